@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- NAF decode throughput on MI355X (BASELINE.json metric: decoded Gbases/s).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--bases B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--bases B] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one synthetic archive already resident in HBM:
 per-block Huffman literal decode of the sequence section, record-length scan, 4-bit -> IUPAC
@@ -11,9 +11,15 @@ blocks).  For N>1 every rank decodes its own 10 GB shard of the N x 10 GB archiv
 scaling, block-range sharding) and the ranks exchange {bases, packed bytes, records, carry}
 with one RCCL all-gather per step to place their records in the global offset table.
 
-Prints ONE JSON line on rank 0 (see the field list in the task contract) with two extra
-objects: "roofline" for the dominant kernel (k_huf_decode) and "cpu_baseline" (the CPU oracle
-timed on a bounded sample of the same workload, one host thread like the reference).
+Prints ONE JSON line on rank 0 (see the field list in the task contract) with "roofline" for the
+dominant kernel (k_huf_decode), from this run's timings.  A plain run does only that: set up, warm
+up, time K steps, print.  --full adds everything else, after the timed steps: the full-size check
+of the output against the writer's checksums, "cpu_baseline" (the CPU oracle timed on a bounded
+sample of the same workload, one host thread like the reference), and the other workloads under
+"path" (masked, real-genome, FASTQ-like, level-3, fixtures, the record iterator; at N>1 the
+real-genome archive through the shard protocol).
+
+--dump-outputs DIR writes what the last timed step computed as .npy files (see dump_outputs).
 """
 import argparse
 import ctypes
@@ -65,7 +71,16 @@ def parse_args():
     ap.add_argument("--rehearsal-lib", default="",
                     help="tests only: run the control flow against another build of the library (the CPU harness); "
                          "the line printed then carries no metric and no value")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the full-size output check, the CPU baseline and the other workloads (the legs above); "
+                         "a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, "
+                         "a fixed sample of the 40 GB output plus checksums of all of it; under 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def cpu_baseline(lib, n_bases_target, mask, device):
@@ -566,6 +581,53 @@ def committed_traffic(n_bases):
     return best
 
 
+DUMP_SEED = 0x4E4146
+DUMP_SEQ_WINDOWS, DUMP_SEQ_WINDOW = 256, 16384     # 4 Mi bases of the sequence = 16 MiB as float32
+DUMP_END_WINDOWS, DUMP_END_WINDOW = 256, 2048      # 512 Ki record ends = 4 MiB as float64
+
+
+def _device_sample(lib, h, d_ptr, n, dtype, windows, window):
+    """-> (values, offsets): the n items of `dtype` at device address d_ptr whole when they fit in windows x window, else
+    `windows` runs of `window` items at positions drawn from DUMP_SEED (the first and the last run always) -- positions
+    that depend on n alone, so that two runs or two builds sample the same items."""
+    import numpy as np
+    if n <= windows * window:
+        starts, window = [0], n
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        starts = sorted({0, n - window, *(int(x) for x in rng.integers(0, n - window + 1, windows - 2))})
+    out = np.empty((len(starts), window), dtype=dtype)
+    for i, s in enumerate(starts):
+        if window and lib.c.nafgpu_copy_to_host(h, d_ptr + s * out.itemsize, window * out.itemsize, out[i].ctypes.data) != 0:
+            raise RuntimeError("dump-outputs: copy to host failed")
+    return out.reshape(-1), np.array(starts, dtype=np.float64)
+
+
+def dump_outputs(lib, h, res, out_dir, world=1):
+    """--dump-outputs: what the last timed step handed its caller (nafgpu_decode_all_device's DeviceResult), as .npy files
+    that two builds can compare output for output, at most 20 MiB in all:
+      sequence.npy, sequence_offsets.npy   float32 characters of the decoded sequence, a fixed sample (_device_sample), and
+                                           float64 where each of its runs starts;
+      record_end.npy, record_end_offsets.npy   float64 record table (end of every record in the sequence), the same way;
+      summary.npy   float64 [n_bases, n_records, base_offset, the 64-bit checksum (csrc/hash64.h) of the WHOLE sequence and
+                    of the WHOLE record table as 32-bit halves, low first] -- every byte of the output takes part.
+    At N>1 every rank writes its own shard into out_dir/rank<r>/ with 1/N of the windows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n_bases, n_records = int(res.n_bases), int(res.n_records)
+    seq, seq_at = _device_sample(lib, h, res.d_sequence, n_bases, np.uint8, max(2, DUMP_SEQ_WINDOWS // world), DUMP_SEQ_WINDOW)
+    ends, ends_at = _device_sample(lib, h, res.d_record_end, n_records, np.uint64, max(2, DUMP_END_WINDOWS // world), DUMP_END_WINDOW)
+    hs, he = ctypes.c_uint64(), ctypes.c_uint64()
+    if (lib.c.nafgpu_hash64_device_at(h, res.d_sequence, n_bases, int(res.base_offset) // 4096, ctypes.byref(hs)) != 0 or
+            lib.c.nafgpu_hash64_device(h, res.d_record_end, 8 * n_records, ctypes.byref(he)) != 0):
+        raise RuntimeError("dump-outputs: checksum on the device failed")
+    summary = [n_bases, n_records, int(res.base_offset), hs.value & 0xFFFFFFFF, hs.value >> 32, he.value & 0xFFFFFFFF, he.value >> 32]
+    for name, a in (("sequence", seq.astype(np.float32)), ("sequence_offsets", seq_at),
+                    ("record_end", ends.astype(np.float64)), ("record_end_offsets", ends_at),
+                    ("summary", np.array(summary, dtype=np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
     rank = int(os.environ.get("RANK", "0"))
@@ -713,9 +775,12 @@ def main():
         total_bases = placement.total_bases
     else:
         total_bases = int(res.n_bases)
+    if args.dump_outputs:
+        dump_outputs(lib, h, res, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank), world)
 
     ok = True
-    if not args.no_verify:                          # bit-exactness at full size: position-keyed checksums (hash64.h)
+    verify = args.full and not args.no_verify
+    if verify:                                      # bit-exactness at full size: position-keyed checksums (hash64.h)
         out = ctypes.c_uint64()
         if world == 1:
             lib.c.nafgpu_hash64_device(h, res.d_sequence, res.n_bases, ctypes.byref(out))
@@ -760,7 +825,7 @@ def main():
                                    % (archive_bytes / 1e9, "+mask" if args.mask else "", ", %d permille IUPAC" % args.iupac if args.iupac else "",
                                       total_bases, res.n_records,
                                       res.n_zstd_blocks, res.n_huf_streams,
-                                      "passed" if (ok and not args.no_verify) else "skipped"),
+                                      "passed" if (ok and verify) else "skipped"),
                        "sharding": ("ONE archive, %d contiguous zstd-block ranges (one per GPU, %.1f GB of compressed bytes uploaded per GPU), "
                                     "one all-gather of {bases, packed bytes, first record, carry} per step" % (world, res.seq_compressed_bytes / 1e9))
                                    if world > 1 else "single GPU"},
@@ -780,17 +845,18 @@ def main():
         # first decode of a fresh archive, everything included: host walk + H2D (PCIe) + the device decode
         e2e_s = (res.ms_host_plan + res.ms_h2d + dev_ms) * 1e-3
         line["path"]["end_to_end_Gbases_s"] = round(total_bases / world / e2e_s / 1e9, 1) if e2e_s > 0 else None
-        if not args.mask and not args.no_masked_leg and not args.iupac and world == 1 and not args.rehearsal_lib:
+        legs = args.full and world == 1 and not args.rehearsal_lib      # the other workloads, after the headline's steps
+        if not args.mask and not args.no_masked_leg and not args.iupac and legs:
             line["path"]["masked"] = masked_leg(lib, device, n_bases)
-        if args.real_copies and world == 1 and not args.rehearsal_lib:
+        if args.real_copies and legs:
             line["path"]["real_genome"] = real_genome_leg(lib, device, args.real_copies)
-        if args.small_real_copies and world == 1 and not args.rehearsal_lib:
+        if args.small_real_copies and legs:
             line["path"]["real_genome_3g"] = real_genome_leg(lib, device, args.small_real_copies)
-        if args.fastq_reads and world == 1 and not args.rehearsal_lib:
+        if args.fastq_reads and legs:
             line["path"]["fastq_like"] = fastq_like_leg(lib, device, int(args.fastq_reads))
-        if args.l3_bases and world == 1 and not args.rehearsal_lib:
+        if args.l3_bases and legs:
             line["path"]["l3_dna"] = l3_dna_leg(lib, device, int(args.l3_bases))
-        if not args.no_iterator and world == 1 and not args.rehearsal_lib:
+        if not args.no_iterator and legs:
             line["path"]["fixtures"] = fixtures_leg(device)
             # the headline archive through the drop-in API: Decoder::from_path + Iterator::next (a file, as the reference reads one)
             import shutil
@@ -803,7 +869,7 @@ def main():
             finally:
                 if os.path.exists(ipath):
                     os.unlink(ipath)
-        if not args.no_cpu and world == 1:       # reported baseline, rank 0 at N=1 only
+        if args.full and not args.no_cpu and world == 1:       # reported baseline, rank 0 at N=1 only
             line["cpu_baseline"], checked = cpu_baseline(lib, args.cpu_sample_bases, args.mask, device)
             line["config"]["oracle_checked_bases"] = checked
             line["config"]["workload"] += "; GPU decode of a %d-base archive of the same generator equals the CPU oracle's output" % checked
@@ -826,7 +892,7 @@ def main():
             line["backend"] = "%s%s" % (dist.get_backend(), " (RCCL over xGMI)" if tdev == "cuda" else "")
             line["rccl_ranks" if tdev == "cuda" else "ranks"] = dist.get_world_size()
             line["devices"] = names
-    if world > 1 and args.real_copies_per_gpu:
+    if world > 1 and args.full and args.real_copies_per_gpu:
         # sections WITH LZ sequences over the same ranks (every rank takes part).  The headline above is already measured: a
         # rank that fails or stalls in this leg must not take the line with it, so the leg runs under a per-rank time limit,
         # after which rank 0 prints the line with the failure named in it and every rank leaves.

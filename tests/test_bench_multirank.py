@@ -26,7 +26,7 @@ def test_bench_contract(world):
     csrc = os.path.join(ROOT, "nafcodec_amd", "csrc")
     subprocess.check_call(["make", "-s", "-C", csrc, "emu"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     env = dict(os.environ, OMP_NUM_THREADS="1")
-    args = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--bases", "600001", "--cpu-sample-bases", "200000",
+    args = ["--full", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--bases", "600001", "--cpu-sample-bases", "200000",
             "--real-copies-per-gpu", "1", "--rehearsal-lib", os.path.join(ROOT, "tests", "emu", "_build", "libnafgpu_emu.so")]
     if world == 1:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + args
@@ -58,6 +58,52 @@ def test_bench_contract(world):
     assert "passed" in j["config"]["workload"]  # the full-size checksum check ran and held on every rank
 
 
+def test_plain_run_times_only_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline alone (no output check, no CPU baseline, no other workload), --steps
+    sets the number of timed steps, and --dump-outputs writes the last step's output: float32 / float64 arrays, the same
+    from run to run, and -- the archive being small enough to be dumped whole -- equal to what the writer wrote."""
+    import ctypes
+
+    import numpy as np
+    from nafcodec_amd import _ffi
+    csrc = os.path.join(ROOT, "nafcodec_amd", "csrc")
+    subprocess.check_call(["make", "-s", "-C", csrc, "emu"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    emu = os.path.join(ROOT, "tests", "emu", "_build", "libnafgpu_emu.so")
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--bases", "600001",
+               "--rehearsal-lib", emu, "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, OMP_NUM_THREADS="1"))
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert (j["steps"], j["warmup"], j["unit"], j["dtype"], j["higher_is_better"]) == (3, 1, "Gbases/s", "u8", True)
+        assert j["ms_per_step"] > 0 and "cpu_baseline" not in j and "skipped" in j["config"]["workload"]
+        assert not {"masked", "real_genome", "real_genome_3g", "fastq_like", "l3_dna", "fixtures", "iterator"} & set(j["path"])
+        files = sorted(os.listdir(out))
+        assert files == ["record_end.npy", "record_end_offsets.npy", "sequence.npy", "sequence_offsets.npy", "summary.npy"]
+        assert sum(os.path.getsize(out / f) for f in files) < 64 << 20
+        arrays = {f: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        dumps.append(arrays)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
+    lib = _ffi.Library(emu)
+    arc = lib.synth(600001, seed=0x4E4146)
+    try:
+        d = dumps[0]
+        seq = d["sequence.npy"].astype(np.uint8).tobytes()
+        ends = d["record_end.npy"].astype(np.uint64)
+        assert list(d["summary.npy"][:3]) == [arc.n_bases, arc.n_records, 0] and len(seq) == arc.n_bases and ends[-1] == arc.n_bases
+        assert lib.c.nafgpu_hash64_host(seq, len(seq)) == arc.seq_hash
+        assert lib.c.nafgpu_hash64_host(ends.tobytes(), ends.nbytes) == arc.offsets_hash
+        assert int(d["summary.npy"][3]) + (int(d["summary.npy"][4]) << 32) == arc.seq_hash
+        assert int(d["summary.npy"][5]) + (int(d["summary.npy"][6]) << 32) == arc.offsets_hash
+    finally:
+        lib.c.nafgpu_synth_free(ctypes.byref(arc))
+
+
 def test_headline_line_survives_a_sharded_leg_that_does_not_finish():
     """The second workload of the multi-rank run has a time limit of its own: when it runs out every rank leaves, and rank 0
     still prints the one line -- with the headline in it and the failure named where the leg's numbers would be (which step
@@ -67,7 +113,7 @@ def test_headline_line_survives_a_sharded_leg_that_does_not_finish():
     csrc = os.path.join(ROOT, "nafcodec_amd", "csrc")
     subprocess.check_call(["make", "-s", "-C", csrc, "emu"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
+           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "0",
            "--bases", "300001", "--real-copies-per-gpu", "1", "--sharded-leg-limit", "0",
            "--rehearsal-lib", os.path.join(ROOT, "tests", "emu", "_build", "libnafgpu_emu.so")]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, OMP_NUM_THREADS="1"))
@@ -104,7 +150,7 @@ def test_three_ranks_share_the_one_gpu():
     world = 3
     env = dict(os.environ, OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
+           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--steps", "2", "--warmup", "1",
            "--bases", "2e9", "--no-cpu", "--rehearsal-one-gpu", "--real-copies-per-gpu", "200"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]

@@ -8,5 +8,6 @@ for pair in "real tools/real_probe.py 3000" "fq tools/fastq_probe.py 10e6" "l3 t
   rm -rf gpurun_out/${tag}_$name
   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_$name -o run -- python3 "$@" > gpurun_out/${tag}_$name.log 2>&1 || exit 1
 done
-python3 bench.py > gpurun_out/${tag}_bench_full.log 2>&1
-tail -1 gpurun_out/${tag}_bench_full.log | cut -c1-200
+# the full bench (every workload, the CPU baseline, the output check) logs straight into profiles/
+python3 bench.py --full > profiles/${tag}_bench_full.log 2>&1
+tail -1 profiles/${tag}_bench_full.log | cut -c1-200

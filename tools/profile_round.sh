@@ -25,5 +25,6 @@ stats mask bench.py --mask --steps 5 --warmup 2 --no-cpu --real-copies 0 --small
 stats real tools/real_probe.py 3000 || exit 1
 stats fq tools/fastq_probe.py 10e6 || exit 1
 stats l3 tools/l3_probe.py 512e6 || exit 1
-python3 bench.py > gpurun_out/${tag}_bench_full.log 2>&1
-tail -1 gpurun_out/${tag}_bench_full.log | cut -c1-600
+# the full bench (every workload, the CPU baseline, the output check) logs straight into profiles/
+python3 bench.py --full > profiles/${tag}_bench_full.log 2>&1
+tail -1 profiles/${tag}_bench_full.log | cut -c1-600
