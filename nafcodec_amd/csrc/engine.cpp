@@ -774,6 +774,12 @@ Failure SectionJob::load_tile(uint32_t t, hipStream_t stream) {
         }
         xxh_live_ = live;
     }
+    // frames with LZ sequences and a Frame_Content_Size: checked once the block sizes are scanned (a frame that spans tiles or
+    // shards is not: its pieces are never added up in one place)
+    fcs_segs_.clear();
+    for (const ZPlan::Frame &f : plan_.frames)
+        if (f.has_fcs && f.first_blk >= tile.b0 && f.end_blk <= tile.b1)
+            fcs_segs_.push_back(FcsSeg{f.first_blk - tile.b0 + plan_.halo, f.end_blk - tile.b0 + plan_.halo, f.fcs});
     if (hook_env("NAFGPU_DEBUG_PLAN")) {
         std::fprintf(stderr, "[nafgpu] section plan: tile %u of %zu, %zu blocks, %zu streams, %zu seq blocks, %llu sequences, literal buffer %llu B, source %llu B; task classes:",
                      t, tiles_.size(), n_blocks_, n_streams_, n_seq_blocks_, static_cast<unsigned long long>(plan_.n_sequences),
@@ -815,6 +821,7 @@ Failure SectionJob::load_tile(uint32_t t, hipStream_t stream) {
         {&d_seq_blocks_, plan_.seq_blocks.data(), n_seq_blocks_ * sizeof(SeqBlock), 0, 0, 0},
         {&d_cells_, plan_.fse_pool.data(), plan_.fse_pool.size() * sizeof(SeqCell), 0, 0, 0},
         {&d_xxh_segs_, xxh_segs_.data(), xxh_segs_.size() * sizeof(XxhSeg), 0, 0, 0},
+        {&d_fcs_segs_, fcs_segs_.data(), fcs_segs_.size() * sizeof(FcsSeg), 0, 0, 0},
     };
     size_t pack_total = 0;
     for (Piece &pc : pieces) {
@@ -862,7 +869,8 @@ Failure SectionJob::load_tile(uint32_t t, hipStream_t stream) {
              d_copies_.upload(plan_.copies.data(), n_copies_ * sizeof(CopyTask), stream) &&
              d_seq_blocks_.upload(plan_.seq_blocks.data(), n_seq_blocks_ * sizeof(SeqBlock), stream) &&
              d_cells_.upload(plan_.fse_pool.data(), plan_.fse_pool.size() * sizeof(SeqCell), stream) &&
-             d_xxh_segs_.upload(xxh_segs_.data(), xxh_segs_.size() * sizeof(XxhSeg), stream);
+             d_xxh_segs_.upload(xxh_segs_.data(), xxh_segs_.size() * sizeof(XxhSeg), stream) &&
+             d_fcs_segs_.upload(fcs_segs_.data(), fcs_segs_.size() * sizeof(FcsSeg), stream);
     }
     ok = ok &&
          d_lit_.alloc(static_cast<size_t>(plan_.lit_bytes) + 64) &&
@@ -1191,6 +1199,7 @@ void SectionJob::run_back(hipStream_t stream, StageTimer *timer, hipStream_t aux
                                 : (!has_lz_ ? halo_elems_ + plan_.known_out : ~0ull);
     launch_scan_blocks(stream, d_blk_size_.as<uint32_t>(), n_blocks_, d_blk_base_.as<uint64_t>(), d_scan_tmp_.bytes(),
                        expect_sel, status);
+    launch_frame_sizes(stream, d_fcs_segs_.as<FcsSeg>(), static_cast<uint32_t>(fcs_segs_.size()), d_blk_base_.as<uint64_t>(), status);
     const bool ascii = t_char_ != 0;
     // kernels address the output as base + position inside the loaded selection
     uint8_t *const out_base = tile_out_base();

@@ -246,7 +246,8 @@ private:
     DevBuf d_halo_tmp_;
     std::vector<XxhSeg> xxh_segs_;                // frame checksums: the (pieces of) checksummed frames in the loaded tile
     bool xxh_live_ = false;                       // ... and whether the frame the next tile continues was begun in this process's range
-    DevBuf d_xxh_segs_, d_xxh_carry_;
+    std::vector<FcsSeg> fcs_segs_;                // frames with LZ sequences and a Frame_Content_Size, whole in the loaded tile
+    DevBuf d_xxh_segs_, d_xxh_carry_, d_fcs_segs_;
     DevBuf d_pj_list_[2];                          // dense LZ sections: lists of pending elements for the late sweeps (optional)
     DevBuf d_pj_dist_, d_pj_tiles_;               // dense LZ sections: one word per output element + one per tile (allocated on first use, kept)
     bool lz_dense_ = false;

@@ -148,6 +148,7 @@ void launch_mask_apply(hipStream_t stream, uint8_t *ascii, uint64_t n_bases, uin
 // Content_Checksum of the frames (pieces of frames) in `segs`: XXH64 over the decoded bytes at out + blk_base[..]
 // (ascii: the section output holds two characters per decoded byte, packed again on the fly); a mismatch flags
 // kStChecksum.  carry_in / carry_out: running state of a frame that spans tiles.
+void launch_frame_sizes(hipStream_t stream, const FcsSeg *segs, uint32_t n_segs, const uint64_t *blk_base, uint32_t *status);
 void launch_xxh64_frames(hipStream_t stream, const XxhSeg *segs, uint32_t n_segs, const uint64_t *blk_base, const uint8_t *out,
                          bool ascii, uint32_t t_char, const XxhCarry *carry_in, XxhCarry *carry_out, uint32_t *status);
 

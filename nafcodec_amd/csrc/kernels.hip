@@ -1752,7 +1752,7 @@ __global__ __launch_bounds__(64) void k_seq_values(const uint8_t *__restrict__ s
             uint32_t o;
             if (ofv > 3) {
                 o = ofv - 3;
-                bad = bad || (o & kRepToken);                // >= 2^31: beyond any legal window
+                bad = bad || (o & kRepToken) || o > sb.window;   // beyond the frame's window (>= 2^31: beyond any legal one)
                 r2 = r1;
                 r1 = r0;
                 r0 = o;
@@ -2056,6 +2056,15 @@ __global__ void k_scan_finish_blocks(uint64_t *blk_base, uint64_t n, const ScanT
     // never told the size, the record that needs the missing bytes fails (Io(UnexpectedEof)) -- and so not here: the host
     // reads the total back (SectionJob::check).  (~0: a tile of a section with sequences -- the host adds the tiles up)
     if (expect != ~0ull && totals->sum > expect) flag_error(status, kStSizeMismatch, 0xFFFFFFFFu);
+}
+
+// Frame_Content_Size of the frames with LZ sequences that the loaded selection holds whole (FcsSeg): one lane per frame.
+__global__ void k_frame_sizes(const FcsSeg *__restrict__ segs, uint32_t n_segs, const uint64_t *__restrict__ blk_base,
+                              uint32_t *status) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_segs || status[0] != 0) return;
+    const FcsSeg f = segs[i];
+    if (blk_base[f.blk1] - blk_base[f.blk0] != f.fcs) flag_error(status, kStSizeMismatch, f.blk0);
 }
 
 // ======================================================================================
@@ -4140,6 +4149,11 @@ void launch_scan_blocks(hipStream_t stream, const uint32_t *blk_size, uint64_t n
     ScanTotals *totals = reinterpret_cast<ScanTotals *>(tiles + (n + kScanTile - 1) / kScanTile);
     scan_generic<kModeExcl>(stream, reinterpret_cast<const uint8_t *>(blk_size), n, blk_base, n, tile_tmp, totals, status);
     hipLaunchKernelGGL(k_scan_finish_blocks, dim3(1), dim3(1), 0, stream, blk_base, n, totals, expect_total, status);
+}
+
+void launch_frame_sizes(hipStream_t stream, const FcsSeg *segs, uint32_t n_segs, const uint64_t *blk_base, uint32_t *status) {
+    if (!n_segs) return;
+    hipLaunchKernelGGL(k_frame_sizes, dim3((n_segs + 63) / 64), dim3(64), 0, stream, segs, n_segs, blk_base, status);
 }
 
 void launch_scan_runs_u32(hipStream_t stream, const uint8_t *words, uint64_t n_words, uint64_t *ends, uint64_t cap,

@@ -7,6 +7,7 @@
 namespace nafgpu {
 
 constexpr uint32_t kBlockMax = 128u << 10;   // zstd Block_Maximum_Size
+constexpr uint64_t kWindowMax = 1ull << 27;  // largest Window_Size accepted: libzstd's default windowLogMax, which the reference's stream decoder keeps
 constexpr int kHufWave = 64;                 // one Huffman stream per lane, one wave per workgroup
 constexpr uint32_t kHufLdsEntries = 2048;    // 8-byte decode-table entries a single-tree wave task may stage in LDS
 constexpr uint32_t kHufLdsEntries4 = 6144;   // 4-byte entries a task with several trees may stage (compact tables, see HufTask)
@@ -123,7 +124,7 @@ struct SeqBlock {        // one compressed block with nbSeq > 0
     uint32_t frame_first_blk;          // first block of the frame this block belongs to
     uint8_t ll_al, of_al, ml_al;
     uint8_t direct;                    // 1: k_huf_decode already put the literals at their final positions (<= kDirectSeqMax sequences)
-    uint32_t pad2;
+    uint32_t window;                   // Window_Size of its frame (clamped to 2^31): a fresh offset beyond it is corrupt
 };
 static_assert(sizeof(SeqBlock) == 64, "SeqBlock layout");
 
@@ -190,6 +191,12 @@ struct XxhSeg {
     uint32_t blk0, blk1;   // blocks [blk0, blk1) of the loaded selection
     uint32_t expected;     // the stored checksum
     uint32_t flags;        // 1: the frame begins with blk0; 2: it ends with blk1 - 1
+};
+// Frame_Content_Size of a frame with LZ sequences (its decoded size is known once the block sizes are scanned): the frame
+// lies in blocks [blk0, blk1) of the loaded selection and must decode to exactly `fcs` bytes.
+struct FcsSeg {
+    uint32_t blk0, blk1;
+    uint64_t fcs;
 };
 struct XxhCarry {
     uint64_t v[4];

@@ -398,7 +398,7 @@ struct Walker {
     }
 
     // one Compressed block occupying [i, end)
-    bool compressed_block(size_t i, size_t end, uint32_t blk, uint32_t frame_first_blk, HufRef *huf,
+    bool compressed_block(size_t i, size_t end, uint32_t blk, uint32_t frame_first_blk, uint64_t window, HufRef *huf,
                           TableRef seqtbl[3]) {
         if (i >= end) return bad("empty compressed block");
         // ---- literals section header
@@ -556,6 +556,7 @@ struct Walker {
         sb.direct = seg ? 1 : 0;
         sb.seq_first = plan->n_sequences;
         sb.frame_first_blk = frame_first_blk;
+        sb.window = static_cast<uint32_t>(std::min<uint64_t>(window, 1ull << 31));
         plan->seq_blocks.push_back(sb);
         plan->n_sequences += nseq;
         if (to_lit) plan->lit_bytes += (regen + 15) & ~size_t(15);       // keep each block's literals 16-B aligned
@@ -589,6 +590,9 @@ struct Walker {
         if (fcs_bytes == 2) fcs += 256;
         i += size_t(fcs_bytes);
         if (single) window = fcs;
+        if (window > kWindowMax) return bad("frame window larger than 128 MiB");
+        // Block_Maximum_Size: min(Window_Size, 128 KiB) for a block's size and an RLE block's regenerated size (RFC 8878 3.1.1.2.3)
+        const uint64_t blk_max = std::min<uint64_t>(window, kBlockMax);
         plan->window_max = std::max(plan->window_max, window);
         plan->n_frames++;
         plan->has_checksum = plan->has_checksum || checksum;
@@ -607,22 +611,22 @@ struct Walker {
             plan->blk_off.push_back(i - 3);
             if (type == 0) {                                   // Raw
                 if (!need(i, bsize, "a raw block")) return false;
-                if (bsize > kBlockMax) return bad("raw block larger than 128 KiB");
+                if (bsize > blk_max) return bad("raw block larger than the block maximum");
                 if (bsize) plan->copies.push_back(CopyTask{i, 0, uint32_t(bsize), blk, 0, 0});
                 plan->blk_size.push_back(uint32_t(bsize));
                 plan->known_out += bsize;
                 i += bsize;
             } else if (type == 1) {                            // RLE
                 if (!need(i, 1, "an RLE block")) return false;
-                if (bsize > kBlockMax) return bad("RLE block larger than 128 KiB");
+                if (bsize > blk_max) return bad("RLE block larger than the block maximum");
                 if (bsize) plan->copies.push_back(CopyTask{p[i], 0, uint32_t(bsize), blk, 2, 0});
                 plan->blk_size.push_back(uint32_t(bsize));
                 plan->known_out += bsize;
                 i += 1;
             } else if (type == 2) {                            // Compressed
                 if (!need(i, bsize, "a compressed block")) return false;
-                if (bsize > kBlockMax) return bad("compressed block larger than 128 KiB");
-                if (!compressed_block(i, i + bsize, blk, frame_first_blk, &huf, seqtbl)) return false;
+                if (bsize > blk_max) return bad("compressed block larger than the block maximum");
+                if (!compressed_block(i, i + bsize, blk, frame_first_blk, window, &huf, seqtbl)) return false;
                 i += bsize;
             } else {
                 return bad("reserved block type");
@@ -630,6 +634,16 @@ struct Walker {
             if (last) break;
         }
         ZPlan::Frame fr{frame_first_blk, static_cast<uint32_t>(plan->blk_size.size()), 0, checksum != 0};
+        if (fcs_bytes) {                                       // Frame_Content_Size: the frame must decode to exactly that
+            const bool lz = !plan->seq_blocks.empty() && plan->seq_blocks.back().frame_first_blk == frame_first_blk &&
+                            plan->seq_blocks.back().blk >= frame_first_blk;
+            uint64_t known = 0;
+            for (uint32_t b = fr.first_blk; b < fr.end_blk; b++) known += plan->blk_size[b];
+            if (!lz && known != fcs) return bad("frame decodes to a size other than its Frame_Content_Size");
+            if (lz && known > fcs) return bad("frame literals exceed its Frame_Content_Size");
+            fr.has_fcs = lz;                                   // (with sequences: on the device, once the block sizes are known)
+            fr.fcs = fcs;
+        }
         if (checksum) {                                        // low 32 bits of XXH64 of the decoded frame, verified on the device
             if (!need(i, 4, "the frame checksum")) return false;
             fr.checksum = uint32_t(p[i]) | (uint32_t(p[i + 1]) << 8) | (uint32_t(p[i + 2]) << 16) | (uint32_t(p[i + 3]) << 24);

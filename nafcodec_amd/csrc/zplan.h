@@ -53,6 +53,8 @@ struct ZPlan {
         uint32_t first_blk, end_blk;     // its blocks
         uint32_t checksum;               // low 32 bits of XXH64 of the decoded frame, when has_checksum
         bool has_checksum;
+        bool has_fcs = false;            // Frame_Content_Size present, and the frame holds LZ sequences (else checked by the walk)
+        uint64_t fcs = 0;
     };
     std::vector<Frame> frames;
     // ---- a selection (select_zplan): blocks [sel_blk0, sel_blk1) of the master, re-based to start at block `halo`

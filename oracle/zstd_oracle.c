@@ -785,6 +785,7 @@ uint64_t zo_xxh64(const uint8_t *p, size_t n)
  * (mod.rs:221-222: the reference feeds the section payload to a zstd stream
  * decoder configured with include_magicbytes(false).)
  */
+#define ZO_WINDOW_MAX ((uint64_t)1 << 27)
 static int decode_frame(const uint8_t *src, size_t n, size_t *consumed, uint8_t *dst, size_t *dpos,
                         size_t dcap, zo_stats *st)
 {
@@ -827,6 +828,11 @@ static int decode_frame(const uint8_t *src, size_t n, size_t *consumed, uint8_t 
     i += (size_t)fcs_bytes;
     if (single)
         window = (size_t)fcs;
+    /* the reference's stream decoder keeps libzstd's default windowLogMax (27) and refuses larger windows */
+    if ((uint64_t)window > ZO_WINDOW_MAX)
+        return -ZO_E_CORRUPT;
+    /* Block_Maximum_Size (RFC 8878 3.1.1.2.3): min(Window_Size, 128 KiB) for Block_Size and an RLE block's size */
+    const size_t blk_max = window < (128u << 10) ? window : (128u << 10);
     if (st) {
         st->frames++;
         st->window = window;
@@ -863,6 +869,10 @@ static int decode_frame(const uint8_t *src, size_t n, size_t *consumed, uint8_t 
                 rc = -ZO_E_TRUNCATED;
                 break;
             }
+            if (bsize > blk_max) {
+                rc = -ZO_E_CORRUPT;
+                break;
+            }
             if (*dpos + bsize > dcap) {
                 rc = -ZO_E_DSTFULL;
                 break;
@@ -875,6 +885,10 @@ static int decode_frame(const uint8_t *src, size_t n, size_t *consumed, uint8_t 
         } else if (type == 1) {
             if (i + 1 > n) {
                 rc = -ZO_E_TRUNCATED;
+                break;
+            }
+            if (bsize > blk_max) {
+                rc = -ZO_E_CORRUPT;
                 break;
             }
             if (*dpos + bsize > dcap) {
@@ -891,7 +905,7 @@ static int decode_frame(const uint8_t *src, size_t n, size_t *consumed, uint8_t 
                 rc = -ZO_E_TRUNCATED;
                 break;
             }
-            if (bsize > (128u << 10)) {
+            if (bsize > blk_max) {
                 rc = -ZO_E_CORRUPT;
                 break;
             }

@@ -553,6 +553,29 @@ def raw_naf(packed=None, n_bases=0, text=None, lens=(), quality=None, level=1, f
     return bytes(blob)
 
 
+def naf_with_payload(payload, decoded_len, kind="dna", lens=None, quality=None, line_length=60, mask_runs=None):
+    """A NAF archive whose Sequence section (kind "dna": 4-bit pairs, 2 * decoded_len bases; "text": decoded_len
+    characters) is the ready-made zstd `payload` (magicless frame(s)); `quality`, when given, is (payload, decoded_len)
+    of a Quality section; `mask_runs`, a Mask section.  Record lengths default to one record over everything."""
+    import zstd_ref
+    n = 2 * decoded_len if kind == "dna" else decoded_len
+    lens = [n] if lens is None else lens
+    words = nw.length_words(lens)
+    head = bytes([1, 0xF9, 0xEC, 1]) if kind == "dna" else bytes([1, 0xF9, 0xEC, 2, 3])
+    flags = 0x0A | (0x01 if quality is not None else 0) | (0x04 if mask_runs is not None else 0)
+    secs = [(len(words), zstd_ref.compress_magicless(words, 1, True))]
+    if mask_runs is not None:
+        mask = nw.mask_bytes(mask_runs)
+        secs.append((len(mask), zstd_ref.compress_magicless(mask, 1, True)))
+    secs.append((n, payload))
+    if quality is not None:
+        secs.append((quality[1], quality[0]))
+    blob = bytearray(head) + bytes([flags, 0x20]) + nw.varint(line_length) + nw.varint(len(lens))
+    for orig, data in secs:
+        blob += nw.varint(orig) + nw.varint(len(data)) + data
+    return bytes(blob)
+
+
 def lz_shard_archives(scale=1):
     """(name, archive bytes, expected sequence bytes, expected quality bytes or None, record lengths) -- archives whose
     sections hold LZ sequences, for the shard protocol: the statistics of a real genome (the reference's fixture tiled,

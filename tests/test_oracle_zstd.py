@@ -96,3 +96,41 @@ def test_corrupt_streams_error_not_crash():
         except oracle.OracleError:
             bad += 1
     assert bad > 0
+
+
+def test_crafted_frames_follow_the_stream_decoder():
+    """Hand-built frames (tests/zstd_craft.py) on which the oracle must give libzstd's streaming verdict: a window above
+    2^27, blocks larger than the window, a content size the blocks do not decode to -- refused; a window of exactly 2^27,
+    a match exactly Window_Size back, a block exactly Window_Size long -- accepted with the same bytes."""
+    import zstd_craft as zc
+    cases = []
+    f = zc.Frame(window_desc=18 << 3)
+    f.raw(b"abc")
+    cases.append(f)
+    f = zc.Frame(window_desc=17 << 3, checksum=True)
+    f.raw(b"abc")
+    cases.append(f)
+    for n in (1024, 1025):
+        f = zc.Frame(window_desc=0)
+        f.raw(bytes(range(256)) * 4)
+        f.rle(9, n)
+        cases.append(f)
+    f = zc.Frame(window_desc=0)
+    f.raw(bytes(range(256)) * 4)
+    f.compressed(b"xy", [(2, 50, 3 + 1024)])
+    cases.append(f)
+    f = zc.Frame(window_log=17, fcs=50, fcs_bytes=4)
+    f.raw(bytes(49))
+    cases.append(f)
+    seen = set()
+    for k, fr in enumerate(cases):
+        p, exp, _ = fr.payload()
+        got, err = zstd_ref.decompress_stream(zstd_ref.ZSTD_MAGIC + p)
+        seen.add(err is None)
+        if err is None:
+            assert got == exp and oracle.zstd_decode(p, len(exp)) == exp, k
+        else:
+            with pytest.raises(oracle.OracleError) as e:
+                oracle.zstd_decode(p, len(exp) + 4096)
+            assert e.value.kind == oracle.E_IO_INVALID, k           # (zo_decode_section: -2 = corrupt)
+    assert seen == {True, False}

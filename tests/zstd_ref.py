@@ -108,3 +108,50 @@ def decompress_magicless(payload: bytes, capacity: int) -> bytes:
     if L.ZSTD_isError(n):
         raise ValueError("libzstd error %d" % n)
     return out.raw[:n]
+
+
+def decompress(frame: bytes, capacity: int):
+    """One-shot ZSTD_decompress of frame(s) WITH the magic -> bytes, or None when libzstd refuses them."""
+    L = lib()
+    out = ctypes.create_string_buffer(max(capacity, 1))
+    n = L.ZSTD_decompress(out, capacity, frame, len(frame))
+    return None if L.ZSTD_isError(n) else out.raw[:n]
+
+
+def decompress_stream(frame: bytes, chunk=4096, limit=1 << 31):
+    """ZSTD_decompressStream with default parameters (windowLogMax 27), the output taken `chunk` bytes at a time -- the
+    reference's zstd::stream::read::Decoder.  -> (bytes decoded, error or None); a frame cut short is an error too."""
+    L = lib()
+    L.ZSTD_createDStream.restype = ctypes.c_void_p
+    L.ZSTD_freeDStream.argtypes = [ctypes.c_void_p]
+    L.ZSTD_decompressStream.restype = ctypes.c_size_t
+    L.ZSTD_decompressStream.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.ZSTD_getErrorName.restype = ctypes.c_char_p
+    L.ZSTD_getErrorName.argtypes = [ctypes.c_size_t]
+    ds = L.ZSTD_createDStream()
+    src = ctypes.create_string_buffer(frame, len(frame)) if frame else ctypes.create_string_buffer(1)
+    buf = ctypes.create_string_buffer(chunk)
+    ib = _Buf(ctypes.cast(src, ctypes.c_void_p), len(frame), 0)
+    out, err, r = [], None, 1
+    total = 0
+    try:
+        while True:
+            ob = _Buf(ctypes.cast(buf, ctypes.c_void_p), chunk, 0)
+            in_before = ib.pos
+            r = L.ZSTD_decompressStream(ctypes.c_void_p(ds), ctypes.byref(ob), ctypes.byref(ib))
+            if L.ZSTD_isError(r):
+                err = L.ZSTD_getErrorName(r).decode()
+                break
+            out.append(buf.raw[:ob.pos])
+            total += ob.pos
+            if total > limit:
+                err = "output limit"
+                break
+            if r == 0 and ib.pos == ib.size:                         # (0: the frame is decoded and flushed)
+                break
+            if ob.pos == 0 and ib.pos == in_before:                 # no progress: the input ends inside a frame
+                err = "frame cut short"
+                break
+    finally:
+        L.ZSTD_freeDStream(ctypes.c_void_p(ds))
+    return b"".join(out), err
