@@ -4,6 +4,7 @@
 // Header :198-237, Flag(s) :80-189, SequenceType :56-73, FormatVersion :46-50) and error.rs.
 #pragma once
 #include <cstdint>
+#include <cstdio>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -194,7 +195,8 @@ private:
 
 inline Decoder Decoder::from_path(const std::string &path) { return DecoderBuilder().with_path(path); }
 
-// ---- Encoder (encoder/mod.rs:46-384).  Host code, as in the reference; see include/nafgpu.h for what is written.
+// ---- Encoder (encoder/mod.rs:46-384).  Host code, as in the reference, unless EncoderBuilder::device() names a GPU:
+// the sections of compression levels 1 and 2 are then compressed by the HIP kernels, to the same bytes.  See include/nafgpu.h.
 class Encoder {      // mod.rs:215-384 (Memory storage)
 public:
     Encoder(Encoder &&o) noexcept : e_(o.e_) { o.e_ = nullptr; }
@@ -246,16 +248,42 @@ public:
     EncoderBuilder &sequence(bool v) { o_.sequence = v; return *this; }
     EncoderBuilder &quality(bool v) { o_.quality = v; return *this; }
     EncoderBuilder &compression_level(int v) { o_.compression_level = v; return *this; }
+    // (no counterpart in the reference) compress the sections on that GPU (-1: the current one); compression_level 1 or 2
+    EncoderBuilder &device(int v) { device_ = v; return *this; }
     Encoder with_memory() const {                                                    // mod.rs:161-163
         nafgpu_encoder *e = nullptr;
         nafgpu_error err{};
         if (nafgpu_encoder_new(&o_, &e, &err) != NAFGPU_OK) throw Error(err);
-        return Encoder(e);
+        Encoder enc(e);
+        if (device_ >= -1) {
+            err.status = nafgpu_encoder_set_device(e, device_);
+            if (err.status != NAFGPU_OK) {
+                std::snprintf(err.message, sizeof err.message, "%s",
+                              err.status == NAFGPU_E_DEVICE ? "no usable HIP device" : "device encoding needs compression_level 1 or 2");
+                throw Error(err);
+            }
+        }
+        return enc;
     }
+    const nafgpu_encoder_opts &options() const { return o_; }
 
 private:
     nafgpu_encoder_opts o_{};
+    int device_ = -2;                                                                // -2: host code
 };
+
+// (no counterpart in the reference) records that are in HBM -> an archive, the bytes Encoder::write gives when the same
+// records are pushed one by one: nafgpu_encode_device.  `fields` says what is written (id / comment / sequence / quality,
+// compression_level 1 or 2); the source's pointers must agree with it.
+inline std::string encode_device(const nafgpu_encode_source &src, const EncoderBuilder &fields, int device = -1) {
+    uint8_t *p = nullptr;
+    uint64_t n = 0;
+    nafgpu_error err{};
+    if (nafgpu_encode_device(&src, &fields.options(), device, &p, &n, &err) != NAFGPU_OK) throw Error(err);
+    std::string out(reinterpret_cast<const char *>(p), n);
+    nafgpu_encode_free(p);
+    return out;
+}
 
 // (no counterpart in the reference: the library keeps device memory of closed decoders for the next one -- nafgpu.h)
 inline void trim_device_memory(int device = -1) { (void)nafgpu_trim_device_memory(device); }

@@ -346,6 +346,42 @@ int nafgpu_encoder_push(nafgpu_encoder *enc, const nafgpu_record *rec, nafgpu_er
 int nafgpu_encoder_finish(nafgpu_encoder *enc, const uint8_t **bytes, uint64_t *n, nafgpu_error *err);
 void nafgpu_encoder_free(nafgpu_encoder *enc);
 
+/* ---- encoding on the device: literal-only sections (compression_level 1 and 2) --------------
+ * The kernels count symbols and write the bit streams; the host decides every block from the counts with the same
+ * function the host encoder uses, so the bytes are those of the host path.  Blocks with LZ sequences stay host-only. */
+
+/* L0 counterpart of nafgpu_zstd_decompress: `src` -> one magicless frame of literal-only blocks, the bytes the host
+ * Encoder writes for this section at compression_level 1.  Host in, host out, the work on the GPU.  Any size: inputs
+ * larger than a slab (a multiple of 64 blocks = 8 MiB, so that slabs end on chunk boundaries and stay independent)
+ * go slab by slab.  *produced > cap: NAFGPU_E_INVALID_ARG with *produced set to the size needed. */
+int nafgpu_zstd_compress(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *produced, int device, nafgpu_error *err);
+
+/* Encoder::write on the GPU for sections already pushed: call before nafgpu_encoder_finish.  device >= 0 or -1 (current):
+ * finish compresses every section with the kernels; never called: host code as before.  NAFGPU_E_INVALID_ARG when the
+ * encoder's compression_level is not 1 or 2 (blocks with LZ sequences are host-only), NAFGPU_E_DEVICE when there is no GPU. */
+int nafgpu_encoder_set_device(nafgpu_encoder *enc, int device);
+
+/* The way back from nafgpu_decode_all_device: records that are in HBM -> an archive, without a host push per record. */
+typedef struct {
+    const uint8_t *d_sequence;  uint64_t n_bases;        /* ASCII letters (DNA/RNA: upper-case IUPAC) or raw text */
+    const uint8_t *d_quality;   uint64_t n_quality;
+    const uint64_t *d_record_end; uint64_t n_records;    /* inclusive prefix sums of record lengths */
+    const uint8_t *d_ids;       uint64_t n_ids_bytes;    /* NUL-terminated, concatenated (as decode_all_device leaves them) */
+    const uint8_t *d_comments;  uint64_t n_comments_bytes;
+} nafgpu_encode_source;   /* a NULL pointer = that field is not written; opts->id/comment/sequence/quality must agree */
+/* The archive nafgpu_encoder_finish gives when the same records are pushed one by one, byte for byte (compression_level 1
+ * or 2, else NAFGPU_E_INVALID_ARG).  The host encoder's checks in bulk: quality total != sequence total, or a last record
+ * end that is not the total: NAFGPU_E_INVALID_LENGTH; ids / comments that are not n_records NUL-terminated strings:
+ * NAFGPU_E_MISSING_FIELD; a letter the nucleotide table refuses (lower case included: no Mask section is written):
+ * NAFGPU_E_INVALID_SEQUENCE.  On any error nothing is produced.  *bytes is malloc'ed: free it with nafgpu_encode_free. */
+int nafgpu_encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts *opts, int device,
+                         uint8_t **bytes, uint64_t *n, nafgpu_error *err);
+void nafgpu_encode_free(uint8_t *bytes);
+/* what the calling thread's last nafgpu_zstd_compress / nafgpu_encode_device took, in milliseconds: k_enc_hist and
+ * k_enc_streams + k_enc_scatter (HIP events, summed over slabs and sections), the host plan between them, the whole call
+ * (tools/encode_probe.py) */
+void nafgpu_encode_last_times(double *hist_ms, double *streams_ms, double *plan_ms, double *total_ms);
+
 /* order-sensitive 64-bit checksum used for full-size parity checks: sum over the 8-byte words w_j of
  * mix64(w_j ^ (j + 1) * K) -- every word is mixed non-linearly with its position before it is added, so
  * byte errors cannot cancel -- see hash64.h */

@@ -87,6 +87,13 @@ class EncoderOpts(Structure):
                 ("reserved", c_uint8 * 3), ("compression_level", ctypes.c_int32), ("threads", c_uint32)]
 
 
+class EncodeSource(Structure):
+    """nafgpu_encode_source: device pointers (ints, e.g. a torch tensor's data_ptr(), or None) and their sizes."""
+    _fields_ = [("d_sequence", c_void_p), ("n_bases", c_uint64), ("d_quality", c_void_p), ("n_quality", c_uint64),
+                ("d_record_end", c_void_p), ("n_records", c_uint64), ("d_ids", c_void_p), ("n_ids_bytes", c_uint64),
+                ("d_comments", c_void_p), ("n_comments_bytes", c_uint64)]
+
+
 READ_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, POINTER(c_uint8), c_uint64)
 SEEK_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, c_int64, c_int)
 
@@ -102,6 +109,7 @@ EXPORTS = [
     "nafgpu_encoder_finish", "nafgpu_encoder_free", "nafgpu_test_hooks",
     "nafgpu_hash64_host_at", "nafgpu_shard_begin", "nafgpu_shard_place", "nafgpu_shard_halo", "nafgpu_shard_export_tail",
     "nafgpu_shard_import_halo", "nafgpu_shard_finish", "nafgpu_next_batch", "nafgpu_trim_device_memory",
+    "nafgpu_zstd_compress", "nafgpu_encoder_set_device", "nafgpu_encode_device", "nafgpu_encode_free", "nafgpu_encode_last_times",
 ]
 
 
@@ -168,6 +176,15 @@ class Library:
         L.nafgpu_shard_finish.argtypes = [c_void_p, POINTER(DeviceResult)]
         L.nafgpu_test_hooks.argtypes = [c_int]
         L.nafgpu_test_hooks.restype = None
+        if hasattr(L, "nafgpu_zstd_compress"):               # (absent from older builds loaded for A/B runs)
+            L.nafgpu_zstd_compress.argtypes = [c_char_p, c_size_t, c_void_p, c_size_t, POINTER(c_size_t), c_int, POINTER(Error)]
+            L.nafgpu_encoder_set_device.argtypes = [c_void_p, c_int]
+            L.nafgpu_encode_device.argtypes = [POINTER(EncodeSource), POINTER(EncoderOpts), c_int, POINTER(c_void_p),
+                                               POINTER(c_uint64), POINTER(Error)]
+            L.nafgpu_encode_free.argtypes = [c_void_p]
+            L.nafgpu_encode_free.restype = None
+            L.nafgpu_encode_last_times.argtypes = [POINTER(ctypes.c_double)] * 4
+            L.nafgpu_encode_last_times.restype = None
 
     # ---- helpers ---------------------------------------------------------------------------
     def zstd_decompress(self, payload: bytes, size: int, device: int = -1) -> bytes:
@@ -178,6 +195,22 @@ class Library:
         if rc != OK:
             raise NafError.from_c(err)
         return buf.raw[:produced.value]
+
+    def zstd_compress(self, data: bytes, device: int = -1) -> bytes:
+        """One section -> one magicless frame of literal-only blocks, written on the GPU (nafgpu_zstd_compress)."""
+        cap = len(data) + 3 * (len(data) // (128 << 10) + 1) + 2      # nothing but raw blocks: the largest frame there is
+        buf = ctypes.create_string_buffer(cap)
+        produced, err = c_size_t(0), Error()
+        rc = self.c.nafgpu_zstd_compress(data, len(data), buf, cap, byref(produced), device, byref(err))
+        if rc != OK:
+            raise NafError.from_c(err)
+        return buf.raw[:produced.value]
+
+    def encode_last_times(self):
+        """-> (hist_ms, streams_ms, plan_ms, total_ms) of this thread's last nafgpu_zstd_compress / nafgpu_encode_device"""
+        h, k, p, t = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        self.c.nafgpu_encode_last_times(byref(h), byref(k), byref(p), byref(t))
+        return h.value, k.value, p.value, t.value
 
     def synth(self, n_bases, seed=0x4E4146, with_mask=False, iupac_permille=0, threads=0, part_rank=0, part_count=1):
         """nafgpu_synth_write: the whole archive, or (part_count > 1) this process's share of its sequence blocks."""

@@ -1,0 +1,99 @@
+// encode.h -- what the host encoder (synth.cpp), the device encoder's front end (encode.cpp) and its kernels
+// (encode.hip) share: the block plan of a literal-only section, and the launchers.
+//
+// A literal-only block is decided by symbol counts alone (plan_block); only writing its four bit streams needs the
+// bytes.  The host path is  count -> plan_block -> emit_block;  the device path is  k_enc_hist -> plan_block on the host
+// -> k_enc_streams / k_enc_scatter.  Both give the same frame, byte for byte.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/nafgpu.h"
+#include "container.h"
+
+namespace nafgpu {
+namespace enc {
+
+constexpr size_t kChunkBlocks = 64;     // blocks encoded as one unit (first block carries a fresh table)
+
+struct HufCode {
+    uint8_t len[256];       // 0 = symbol absent
+    uint16_t code[256];
+    uint8_t weight[256];
+    int max_bits = 0;
+    int max_sym = -1;
+    bool valid = false;
+};
+
+enum BlockMode : uint8_t { kRaw = 0, kRle = 1, kHufNew = 2, kHufTreeless = 3 };
+
+struct BlockPlan {
+    BlockMode mode = kRaw;
+    HufCode code{};              // kHufNew / kHufTreeless: the table the four streams are written with
+    std::vector<uint8_t> head;   // everything in front of the streams: block header, then -- raw: nothing more (the bytes follow);
+                                 // RLE: the byte; Huffman: literals header, tree description (new tree), 6-byte jump table
+    uint32_t stream_size[4] = {0, 0, 0, 0};
+    size_t n = 0;                // bytes the block holds
+    size_t total = 0;            // bytes the block takes in the frame
+};
+
+// per-stream symbol counts of one block: q = (n + 3) / 4, streams [0,q) [q,2q) [2q,3q) [3q,n)
+void count_block(const uint8_t *data, size_t n, uint32_t counts[4][256]);
+// Every decision about one block.  `counts` is not read when n < 64 (raw).  *prev: the table of the block before in the
+// same chunk; replaced only when this block is emitted compressed with a new tree.
+void plan_block(const uint32_t counts[4][256], size_t n, bool last, HufCode *prev, BlockPlan *plan);
+void emit_block(const BlockPlan &plan, const uint8_t *data, std::vector<uint8_t> &out);
+
+// one section -> one magicless frame (host code; lz: blocks with LZ sequences, compression levels 0 and >= 3)
+void compress_section(const std::vector<uint8_t> &data, unsigned n_threads, bool lz, std::vector<uint8_t> &out);
+int nucleotide_code(uint8_t c, uint8_t sequence_type);
+void put_varint(std::vector<uint8_t> &out, uint64_t v);
+// header, flags, line length, record count: what stands in front of the sections (encoder/mod.rs:327-347)
+void put_archive_head(std::vector<uint8_t> &out, const nafgpu_encoder_opts &opt, uint64_t n_records);
+
+// ---- the device path (encode.cpp) --------------------------------------------------------------
+struct EncTimes {            // milliseconds, summed over the slabs and sections of one call
+    double hist = 0;         // HIP events around k_enc_hist
+    double streams = 0;      // HIP events around k_enc_streams + k_enc_scatter
+    double plan = 0;         // host: plan_block over the histograms and building the upload
+    double total = 0;        // wall time of the call
+};
+// `src` (host memory, or device memory when src_on_device) -> the frame compress_section(data, ., false) gives, appended to `out`
+Failure compress_section_device(const uint8_t *src, size_t n, bool src_on_device, int device, unsigned n_threads,
+                                std::vector<uint8_t> &out, EncTimes *times);
+
+// ---- kernels (encode.hip); all pointers are device pointers, every launch is asynchronous ---------
+struct EncStream {           // one Huffman stream of one block
+    uint64_t src;            // offset of its first symbol in the slab
+    uint64_t dst;            // offset of its first byte in the slab's output
+    uint32_t n_sym;          // <= 32768
+    uint32_t size;           // bytes, as planned
+    uint32_t table;          // index into the tables
+    uint32_t pad;
+};
+struct EncTable {
+    uint16_t code[256];
+    uint8_t len[256];
+};
+struct EncCopy {             // k_enc_scatter: `len` bytes to out + dst, from the header blob or from the slab's input
+    uint64_t src;
+    uint64_t dst;
+    uint32_t len;
+    uint32_t from_input;
+};
+constexpr uint32_t kEncStBadLetter = 1, kEncStStreamSize = 2;    // status[0] bits; status[2..3]: u64, the complement of the first bad letter's index
+
+void launch_enc_pack(hipStream_t stream, const uint8_t *ascii, uint64_t n, uint8_t sequence_type, uint8_t *packed, uint32_t *status);
+void launch_enc_length_counts(hipStream_t stream, const uint64_t *rec_end, uint64_t n_rec, uint64_t *counts);
+void launch_enc_length_words(hipStream_t stream, const uint64_t *rec_end, uint64_t n_rec, const uint64_t *offsets, uint32_t *words);
+void launch_enc_hist(hipStream_t stream, const uint8_t *src, uint64_t n, uint32_t n_blocks, uint32_t *hist);
+void launch_enc_streams(hipStream_t stream, const uint8_t *src, const EncStream *streams, uint32_t n_streams, const EncTable *tables,
+                        uint32_t max_stream_size, uint8_t *out, uint32_t *status);
+void launch_enc_scatter(hipStream_t stream, const uint8_t *src, const uint8_t *blob, const EncCopy *copies, uint32_t n_copies,
+                        uint8_t *out);
+
+}  // namespace enc
+}  // namespace nafgpu

@@ -1546,6 +1546,9 @@ private:
 };
 }  // namespace
 
+hipStream_t pooled_stream_get(int device) { return StreamPool::instance().get(device); }
+void pooled_stream_put(int device, hipStream_t s) { StreamPool::instance().put(device, s); }
+
 ArchiveJob::~ArchiveJob() {
     if (stream_ || aux_stream_ || k2_stream_) (void)hipSetDevice(device_);
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);

@@ -264,6 +264,10 @@ struct ArchiveOptions {
     bool tiled_output = false;                  // ... whose output is held one tile at a time (iterator path; not for decode_all_device)
 };
 
+// a stream of the pool that closed decoders leave theirs in (engine.cpp: StreamPool); the current device is `device`.
+// put: the stream is synchronised and kept for the next taker
+hipStream_t pooled_stream_get(int device);
+void pooled_stream_put(int device, hipStream_t s);
 bool upload_staged(uint8_t *d_dst, const uint8_t *src, size_t n, hipStream_t stream, size_t stage_min = 0);
 void trim_device_memory(int device);             // engine.cpp: the idle mapped ranges and small buffers of `device` go back to the driver   // engine.cpp: large host -> device copies
 

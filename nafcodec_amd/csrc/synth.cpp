@@ -19,8 +19,11 @@
 #include <vector>
 
 #include "../../include/nafgpu.h"
+#include "encode.h"
 #include "hash64.h"
 #include "plan.h"
+
+using namespace nafgpu::enc;
 
 namespace {
 
@@ -39,6 +42,9 @@ struct Rng {
     double uniform() { return (next() >> 11) * (1.0 / 9007199254740992.0); }
 };
 
+}  // namespace
+namespace nafgpu {
+namespace enc {
 void put_varint(std::vector<uint8_t> &out, uint64_t v) {   // encoder/mod.rs:22-35
     uint8_t tmp[10];
     int k = 0;
@@ -50,6 +56,9 @@ void put_varint(std::vector<uint8_t> &out, uint64_t v) {   // encoder/mod.rs:22-
     }
     while (k) out.push_back(tmp[--k]);
 }
+}  // namespace enc
+}  // namespace nafgpu
+namespace {
 
 // a section of raw zstd blocks (what masked.naf uses for its small sections)
 void raw_frame(const std::vector<uint8_t> &data, std::vector<uint8_t> &out) {
@@ -71,14 +80,6 @@ void raw_frame(const std::vector<uint8_t> &data, std::vector<uint8_t> &out) {
 // ---------------------------------------------------------------- Huffman code construction
 inline int highbit(uint32_t v) { return 31 - __builtin_clz(v); }
 
-struct HufCode {
-    uint8_t len[256];       // 0 = symbol absent
-    uint16_t code[256];
-    uint8_t weight[256];
-    int max_bits = 0;
-    int max_sym = -1;
-    bool valid = false;
-};
 
 // code lengths limited to 11 bits (counts are halved until the tree is shallow enough)
 bool build_lengths(const uint32_t *count, uint8_t *len) {
@@ -341,25 +342,49 @@ void encode_stream(const HufCode &h, const uint8_t *sym, size_t n, std::vector<u
     out.push_back(acc & 0xFF);
 }
 
-// Appends one zstd block (header included) holding `n` literal bytes and no sequences.
-// `prev` is the table of the previous block in the same chunk (treeless reuse) and is updated.
-void encode_block(const uint8_t *data, size_t n, bool last, HufCode *prev, std::vector<uint8_t> &out) {
+}  // namespace
+namespace nafgpu {
+namespace enc {
+
+void count_block(const uint8_t *data, size_t n, uint32_t counts[4][256]) {
+    std::memset(counts, 0, 4 * 256 * sizeof(uint32_t));
+    const size_t q = (n + 3) / 4;
+    for (int k = 0; k < 4; k++) {
+        const size_t a = std::min(n, k * q), b = k == 3 ? n : std::min(n, (k + 1) * q);
+        for (size_t i = a; i < b; i++) counts[k][data[i]]++;
+    }
+}
+
+// What one zstd block holding `n` literal bytes and no sequences looks like, from the symbol counts of its four streams:
+// the size of a stream is floor(sum(count[s] * len[s]) / 8) + 1 (encode_stream: whole bytes, then one byte with the end mark).
+void plan_block(const uint32_t counts[4][256], size_t n, bool last, HufCode *prev, BlockPlan *plan) {
+    BlockPlan &p = *plan;
+    p.head.clear();
+    p.n = n;
+    auto block_header = [&](size_t size, uint32_t type) {
+        const uint32_t bh = static_cast<uint32_t>(size << 3) | (type << 1) | (last ? 1u : 0u);
+        p.head.push_back(bh & 0xFF);
+        p.head.push_back((bh >> 8) & 0xFF);
+        p.head.push_back((bh >> 16) & 0xFF);
+    };
     auto raw_block = [&]() {
-        const uint32_t bh = static_cast<uint32_t>(n << 3) | (last ? 1u : 0u);
-        out.push_back(bh & 0xFF);
-        out.push_back((bh >> 8) & 0xFF);
-        out.push_back((bh >> 16) & 0xFF);
-        out.insert(out.end(), data, data + n);
+        p.mode = kRaw;
+        p.head.clear();
+        block_header(n, 0);
+        p.total = 3 + n;
     };
     if (n < 64) return raw_block();
-    uint32_t count[256] = {0};
-    for (size_t i = 0; i < n; i++) count[data[i]]++;
-    if (count[data[0]] == n) {                                   // one byte value: an RLE block (Huffman needs two symbols)
-        const uint32_t bh = static_cast<uint32_t>(n << 3) | (1u << 1) | (last ? 1u : 0u);
-        out.push_back(bh & 0xFF);
-        out.push_back((bh >> 8) & 0xFF);
-        out.push_back((bh >> 16) & 0xFF);
-        out.push_back(data[0]);
+    uint32_t count[256];
+    int first = -1;
+    for (int s = 0; s < 256; s++) {
+        count[s] = counts[0][s] + counts[1][s] + counts[2][s] + counts[3][s];
+        if (count[s] && first < 0) first = s;
+    }
+    if (count[first] == n) {                                     // one byte value: an RLE block (Huffman needs two symbols)
+        p.mode = kRle;
+        block_header(n, 1);
+        p.head.push_back(static_cast<uint8_t>(first));
+        p.total = 4;
         return;
     }
     HufCode cur{};
@@ -388,21 +413,15 @@ void encode_block(const uint8_t *data, size_t n, bool last, HufCode *prev, std::
     if (cost_new == UINT64_MAX && cost_old == UINT64_MAX) return raw_block();
     const bool treeless = cost_old <= cost_new;
     const HufCode &h = treeless ? *prev : cur;
-    std::vector<uint8_t> body;                                   // tree + jump table + streams
-    if (!treeless) body = tree;
-    const size_t q = (n + 3) / 4;
-    std::vector<uint8_t> st[4];
-    encode_stream(h, data, q, st[0]);
-    encode_stream(h, data + q, q, st[1]);
-    encode_stream(h, data + 2 * q, q, st[2]);
-    encode_stream(h, data + 3 * q, n - 3 * q, st[3]);
-    for (int k = 0; k < 3; k++) {
-        if (st[k].size() > 0xFFFF) return raw_block();
-        body.push_back(st[k].size() & 0xFF);
-        body.push_back(static_cast<uint8_t>(st[k].size() >> 8));
+    size_t comp = treeless ? 0 : tree.size();                    // tree + jump table + streams
+    for (int k = 0; k < 4; k++) {
+        uint64_t bits = 0;
+        for (int s = 0; s < 256; s++) bits += static_cast<uint64_t>(counts[k][s]) * h.len[s];
+        p.stream_size[k] = static_cast<uint32_t>(bits / 8 + 1);
+        if (k < 3 && p.stream_size[k] > 0xFFFF) return raw_block();
+        comp += p.stream_size[k];
     }
-    for (int k = 0; k < 4; k++) body.insert(body.end(), st[k].begin(), st[k].end());
-    const size_t comp = body.size();
+    comp += 6;
     // literals header: 4 streams, size format by magnitude
     uint8_t lh[5];
     size_t lhn;
@@ -422,18 +441,47 @@ void encode_block(const uint8_t *data, size_t n, bool last, HufCode *prev, std::
     }
     const size_t bsize = lhn + comp + 1;                         // + "0 sequences" byte
     if (bsize >= n || bsize > kBlockMax) return raw_block();
-    const uint32_t bh = static_cast<uint32_t>(bsize << 3) | (2u << 1) | (last ? 1u : 0u);
-    out.push_back(bh & 0xFF);
-    out.push_back((bh >> 8) & 0xFF);
-    out.push_back((bh >> 16) & 0xFF);
-    out.insert(out.end(), lh, lh + lhn);
-    out.insert(out.end(), body.begin(), body.end());
-    out.push_back(0x00);                                         // Number_of_Sequences = 0
+    p.mode = treeless ? kHufTreeless : kHufNew;
+    p.code = h;
+    block_header(bsize, 2);
+    p.head.insert(p.head.end(), lh, lh + lhn);
+    if (!treeless) p.head.insert(p.head.end(), tree.begin(), tree.end());
+    for (int k = 0; k < 3; k++) {
+        p.head.push_back(p.stream_size[k] & 0xFF);
+        p.head.push_back(static_cast<uint8_t>(p.stream_size[k] >> 8));
+    }
+    p.total = 3 + bsize;
     if (!treeless) *prev = cur;
 }
 
+// Appends the block: what plan_block decided, then the bytes (raw) or the four streams and the "0 sequences" byte.
+void emit_block(const BlockPlan &p, const uint8_t *data, std::vector<uint8_t> &out) {
+    out.insert(out.end(), p.head.begin(), p.head.end());
+    if (p.mode == kRaw) out.insert(out.end(), data, data + p.n);
+    if (p.mode != kHufNew && p.mode != kHufTreeless) return;
+    const size_t q = (p.n + 3) / 4;
+    encode_stream(p.code, data, q, out);
+    encode_stream(p.code, data + q, q, out);
+    encode_stream(p.code, data + 2 * q, q, out);
+    encode_stream(p.code, data + 3 * q, p.n - 3 * q, out);
+    out.push_back(0x00);                                         // Number_of_Sequences = 0
+}
+
+}  // namespace enc
+}  // namespace nafgpu
+namespace {
+
+// Appends one zstd block (header included) holding `n` literal bytes and no sequences.
+// `prev` is the table of the previous block in the same chunk (treeless reuse) and is updated.
+void encode_block(const uint8_t *data, size_t n, bool last, HufCode *prev, std::vector<uint8_t> &out) {
+    uint32_t counts[4][256];
+    if (n >= 64) count_block(data, n, counts);
+    BlockPlan plan;
+    plan_block(counts, n, last, prev, &plan);
+    emit_block(plan, data, out);
+}
+
 // ---------------------------------------------------------------- the archive
-constexpr size_t kChunkBlocks = 64;     // blocks encoded as one unit (first block carries a fresh table)
 
 struct MaskRun {
     uint64_t start, end;                // masked interval in base coordinates
@@ -953,7 +1001,8 @@ void encode_block_lz(const uint8_t *data, size_t chunk0, size_t b0, size_t n, bo
 // ======================================================================================
 // Encoder (EncoderBuilder / Encoder / SequenceWriter: encoder/mod.rs:46-384, writer.rs:6-100)
 // ======================================================================================
-namespace {
+namespace nafgpu {
+namespace enc {
 
 // one section -> one magicless frame of 128 KiB Huffman-literal blocks; chunks of kChunkBlocks blocks in parallel
 void compress_section(const std::vector<uint8_t> &data, unsigned n_threads, bool lz, std::vector<uint8_t> &out) {
@@ -1017,6 +1066,26 @@ int nucleotide_code(uint8_t c, uint8_t sequence_type) {
     }
 }
 
+void put_archive_head(std::vector<uint8_t> &o, const nafgpu_encoder_opts &opt, uint64_t n_records) {
+    o.insert(o.end(), {0x01, 0xF9, 0xEC});                                           // mod.rs:327
+    uint8_t flags = 0;                                                               // mod.rs:176-193
+    if (opt.id) flags |= 0x20;
+    if (opt.comment) flags |= 0x10;
+    if (opt.sequence) flags |= 0x02 | 0x08;
+    if (opt.quality) flags |= 0x01 | 0x08;
+    if (opt.sequence_type == 0) {                                                    // V1 for DNA, V2 else (mod.rs:169-173, 329-342)
+        o.insert(o.end(), {0x01, flags, ' '});
+    } else {
+        o.insert(o.end(), {0x02, opt.sequence_type, flags, ' '});
+    }
+    put_varint(o, 60);                                                               // Header::default().line_length (data.rs:246)
+    put_varint(o, n_records);
+}
+
+}  // namespace enc
+}  // namespace nafgpu
+namespace {
+
 void put_length_words(std::vector<uint8_t> &out, uint64_t l) {   // write_length, encoder/mod.rs:37-44
     auto word = [&](uint32_t w) {
         for (int k = 0; k < 4; k++) out.push_back(static_cast<uint8_t>(w >> (8 * k)));
@@ -1047,6 +1116,7 @@ struct nafgpu_encoder {
     uint64_t n_records = 0;
     std::vector<uint8_t> archive;
     bool finished = false;
+    int device = -2;                                    // >= -1: finish compresses the sections on that GPU (nafgpu_encoder_set_device)
 };
 
 extern "C" void nafgpu_encoder_opts_default(uint8_t sequence_type, nafgpu_encoder_opts *opts) {
@@ -1145,22 +1215,16 @@ extern "C" int nafgpu_encoder_finish(nafgpu_encoder *e, const uint8_t **bytes, u
             e->cache = -1;
         }
         std::vector<uint8_t> &o = e->archive;
-        o.insert(o.end(), {0x01, 0xF9, 0xEC});                                       // mod.rs:327
-        uint8_t flags = 0;                                                           // mod.rs:176-193
-        if (e->opt.id) flags |= 0x20;
-        if (e->opt.comment) flags |= 0x10;
-        if (e->opt.sequence) flags |= 0x02 | 0x08;
-        if (e->opt.quality) flags |= 0x01 | 0x08;
-        if (e->opt.sequence_type == 0) {                                             // V1 for DNA, V2 else (mod.rs:169-173, 329-342)
-            o.insert(o.end(), {0x01, flags, ' '});
-        } else {
-            o.insert(o.end(), {0x02, e->opt.sequence_type, flags, ' '});
-        }
-        put_varint(o, 60);                                                           // Header::default().line_length (data.rs:246)
-        put_varint(o, e->n_records);
+        put_archive_head(o, e->opt, e->n_records);
+        nafgpu::Failure dev_fail;
         auto block = [&](const std::vector<uint8_t> &data, uint64_t original) {      // write_block!, mod.rs:349-367
             std::vector<uint8_t> frame;
-            compress_section(data, e->opt.threads, e->opt.compression_level == 0 || e->opt.compression_level >= 3, frame);
+            if (e->device >= -1) {
+                if (dev_fail.ok()) dev_fail = compress_section_device(data.data(), data.size(), false, e->device, e->opt.threads, frame, nullptr);
+                if (!dev_fail.ok()) return;
+            } else {
+                compress_section(data, e->opt.threads, e->opt.compression_level == 0 || e->opt.compression_level >= 3, frame);
+            }
             put_varint(o, original);
             put_varint(o, frame.size());
             o.insert(o.end(), frame.begin(), frame.end());
@@ -1170,6 +1234,11 @@ extern "C" int nafgpu_encoder_finish(nafgpu_encoder *e, const uint8_t **bytes, u
         block(e->lens, e->lens.size());                                              // always, whatever the flags say (mod.rs:371)
         if (e->opt.sequence) block(e->seq, e->seq_letters);                          // letters, not bytes (the counter wraps the SequenceWriter)
         if (e->opt.quality) block(e->qual, e->qual.size());
+        if (!dev_fail.ok()) {                                                        // nothing is written; the sections stay for another try
+            o.clear();
+            dev_fail.to_c(err);
+            return dev_fail.status;
+        }
         e->finished = true;
         std::vector<uint8_t>().swap(e->ids);
         std::vector<uint8_t>().swap(e->coms);
@@ -1179,6 +1248,16 @@ extern "C" int nafgpu_encoder_finish(nafgpu_encoder *e, const uint8_t **bytes, u
     }
     *bytes = e->archive.data();
     *n = e->archive.size();
+    return NAFGPU_OK;
+}
+
+extern "C" int nafgpu_encoder_set_device(nafgpu_encoder *e, int device) {
+    if (!e || device < -1 || e->finished) return NAFGPU_E_INVALID_ARG;
+    if (e->opt.compression_level != 1 && e->opt.compression_level != 2) return NAFGPU_E_INVALID_ARG;   // blocks with LZ sequences are host-only
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return NAFGPU_E_DEVICE;
+    if (device >= count) return NAFGPU_E_INVALID_ARG;
+    e->device = device;
     return NAFGPU_OK;
 }
 

@@ -1,6 +1,8 @@
 """Encoder -- same names, arguments and error behaviour as the reference's Python API
 (nafcodec-py/nafcodec/lib.pyi:69-87, lib.rs:463-600; the Rust side: encoder/mod.rs:46-384).  Host code, like the
-reference's; every section is written as Huffman-literal Zstandard blocks (include/nafgpu.h: Encoder)."""
+reference's; every section is written as Huffman-literal Zstandard blocks (include/nafgpu.h: Encoder).  With `device=` the
+sections of compression levels 1 and 2 are compressed by the HIP kernels instead (same bytes), and `encode_device` writes
+an archive from records that are already in HBM."""
 import ctypes
 import os
 from ctypes import byref, c_uint64, c_void_p
@@ -13,7 +15,7 @@ class Encoder:
     """lib.pyi:69-87.  `file` is a path or a binary file-like object; the archive is written by close()."""
 
     def __init__(self, file, sequence_type="dna", *, id=False, comment=False, sequence=False, quality=False,
-                 compression_level=0, _lib=None):
+                 compression_level=0, device=None, _lib=None):
         if sequence_type not in SEQUENCE_TYPES:
             raise ValueError("expected 'dna', 'rna', 'protein' or 'text', got %r" % (sequence_type,))   # lib.rs:487-495
         self._lib = _lib or _ffi.default()
@@ -29,6 +31,14 @@ class Encoder:
         if self._lib.c.nafgpu_encoder_new(byref(opts), byref(h), byref(err)) != _ffi.OK:
             raise _ffi.NafError.from_c(err)
         self._h = h
+        if device is not None:                               # an int: the sections are compressed on that GPU (levels 1 and 2)
+            rc = self._lib.c.nafgpu_encoder_set_device(h, int(device))
+            if rc != _ffi.OK:
+                self._h = None
+                self._lib.c.nafgpu_encoder_free(h)
+                if rc == _ffi.E_INVALID_ARG:
+                    raise ValueError("device encoding writes literal-only blocks: compression_level 1 or 2, and an existing device")
+                raise _ffi.NafError(rc, message="no usable HIP device")
         if isinstance(file, (str, bytes, os.PathLike)):      # fail now, as the reference does when it creates the file
             self._out = open_binary(file)
         else:
@@ -93,9 +103,49 @@ class Encoder:
             self._h = None
 
 
+def zstd_compress(data, device=0, _lib=None):
+    """One section's bytes -> the magicless Zstandard frame the Encoder writes for it at compression_level 1, on the GPU."""
+    return (_lib or _ffi.default()).zstd_compress(bytes(data), device)
+
+
+def encode_device(result, *, sequence_type="dna", id=False, comment=False, sequence=False, quality=False, compression_level=1,
+                  device=None, threads=0, _lib=None):
+    """Records in HBM -> an archive (bytes), equal to what Encoder writes when the same records are pushed one by one.
+    `result` is what Decoder.decode_all_device() returns, or anything with its fields (d_sequence / n_bases, d_quality /
+    n_quality, d_record_end / n_records, d_ids / n_ids_bytes, d_comments / n_comments_bytes) holding device addresses --
+    a torch tensor's data_ptr() will do.  Only the enabled fields are read."""
+    if sequence_type not in SEQUENCE_TYPES:
+        raise ValueError("expected 'dna', 'rna', 'protein' or 'text', got %r" % (sequence_type,))
+    lib = _lib or _ffi.default()
+    opts = _ffi.EncoderOpts()
+    lib.c.nafgpu_encoder_opts_default(SEQUENCE_TYPES.index(sequence_type), byref(opts))
+    opts.id, opts.comment, opts.sequence, opts.quality = map(int, (id, comment, sequence, quality))
+    opts.compression_level, opts.threads = int(compression_level), int(threads)
+    src = _ffi.EncodeSource()
+    src.n_records, src.d_record_end = int(result.n_records), result.d_record_end
+    if id:
+        src.d_ids, src.n_ids_bytes = result.d_ids, int(result.n_ids_bytes)
+    if comment:
+        src.d_comments, src.n_comments_bytes = result.d_comments, int(result.n_comments_bytes)
+    if sequence:
+        src.d_sequence, src.n_bases = result.d_sequence, int(result.n_bases)
+    if quality:
+        src.d_quality, src.n_quality = result.d_quality, int(result.n_quality)
+    p, n, err = c_void_p(), c_uint64(), _ffi.Error()
+    rc = lib.c.nafgpu_encode_device(byref(src), byref(opts), -1 if device is None else int(device), byref(p), byref(n), byref(err))
+    if rc in (_ffi.E_MISSING_FIELD, _ffi.E_INVALID_LENGTH, _ffi.E_INVALID_SEQUENCE, _ffi.E_INVALID_ARG):
+        raise ValueError(err.message.decode("utf-8", "replace"))
+    if rc != _ffi.OK:
+        raise _ffi.NafError.from_c(err)
+    try:
+        return ctypes.string_at(p, n.value)
+    finally:
+        lib.c.nafgpu_encode_free(p)
+
+
 def open_binary(path):
     import builtins
     return builtins.open(os.fspath(path), "wb")
 
 
-__all__ = ["Encoder", "Record"]
+__all__ = ["Encoder", "Record", "encode_device", "zstd_compress"]
