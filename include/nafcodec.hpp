@@ -248,6 +248,9 @@ public:
     EncoderBuilder &sequence(bool v) { o_.sequence = v; return *this; }
     EncoderBuilder &quality(bool v) { o_.quality = v; return *this; }
     EncoderBuilder &compression_level(int v) { o_.compression_level = v; return *this; }
+    // (no counterpart in the reference, whose mask writer is commented out, mod.rs:240) accept lower-case nucleotides and
+    // write their runs as a Mask section; DNA / RNA with sequence(true) only, else with_memory() throws (NAFGPU_E_INVALID_ARG)
+    EncoderBuilder &mask(bool v) { o_.mask = v; return *this; }
     // (no counterpart in the reference) compress the sections on that GPU (-1: the current one); compression_level 1 or 2
     EncoderBuilder &device(int v) { device_ = v; return *this; }
     Encoder with_memory() const {                                                    // mod.rs:161-163
@@ -274,7 +277,7 @@ private:
 
 // (no counterpart in the reference) records that are in HBM -> an archive, the bytes Encoder::write gives when the same
 // records are pushed one by one: nafgpu_encode_device.  `fields` says what is written (id / comment / sequence / quality,
-// compression_level 1 or 2); the source's pointers must agree with it.
+// mask, compression_level 1 or 2); the source's pointers must agree with it.
 inline std::string encode_device(const nafgpu_encode_source &src, const EncoderBuilder &fields, int device = -1) {
     uint8_t *p = nullptr;
     uint64_t n = 0;

@@ -322,19 +322,26 @@ void nafgpu_synth_free(nafgpu_synth_archive *a);
  * blocks -- Huffman / RLE / raw literals, and at `compression_level` 0 (the default level) or >= 3 greedy hash
  * matches coded as sequences with the predefined FSE tables (levels 1-2: literals only) -- which the reference's
  * decoder, libzstd and this library all read.  Sections are kept in memory until the archive is written (the
- * reference's `Memory` storage, storage.rs).  Like the reference's encoder it never writes a Mask section and
- * accepts upper-case IUPAC letters only. */
+ * reference's `Memory` storage, storage.rs).  By default, like the reference's encoder, it writes no Mask section and
+ * accepts upper-case IUPAC letters only.  With `mask` set (nucleotide sequences only: `sequence` != 0 and
+ * `sequence_type` 0 or 1, else NAFGPU_E_INVALID_ARG) lower-case letters are accepted, packed as their upper-case
+ * forms, and a Mask section (flag 0x04, between Length and Sequence) records their runs as MaskReader
+ * (reader.rs:198-231) reads them: over the concatenated letters of all records the maximal runs of equal case,
+ * alternating and starting with an unmasked one (of length 0 when the first letter is lower case), a run of length
+ * l as l / 255 bytes 0xFF and one byte l % 255; nothing behind the last letter, no letters: an empty section. */
 typedef struct {
     uint8_t sequence_type;       /* 0 dna, 1 rna, 2 protein, 3 text (EncoderBuilder::new, mod.rs:81-90) */
     uint8_t id, comment, sequence, quality;   /* opt-in fields (mod.rs:112-145); all 0 by default */
-    uint8_t reserved[3];
+    uint8_t mask;                /* write a Mask section from the case of the letters (see above); 0 by default */
+    uint8_t reserved[2];
     int32_t compression_level;   /* mod.rs:147-157; 0 or >= 3: with LZ matches, 1-2: literals only (see above) */
     uint32_t threads;            /* blocks are encoded in parallel when the archive is written; 0 = hardware concurrency */
 } nafgpu_encoder_opts;
 typedef struct nafgpu_encoder nafgpu_encoder;
 
 void nafgpu_encoder_opts_default(uint8_t sequence_type, nafgpu_encoder_opts *opts);
-/* EncoderBuilder::from_flags (mod.rs:92-110): NAF flag bits 0x20 id, 0x10 comment, 0x02 sequence, 0x01 quality */
+/* EncoderBuilder::from_flags (mod.rs:92-110): NAF flag bits 0x20 id, 0x10 comment, 0x02 sequence, 0x01 quality
+ * (0x04 is ignored, as there: `mask` is set by hand) */
 void nafgpu_encoder_opts_from_flags(uint8_t sequence_type, uint8_t flags, nafgpu_encoder_opts *opts);
 /* EncoderBuilder::with_memory (mod.rs:161-163) */
 int nafgpu_encoder_new(const nafgpu_encoder_opts *opts, nafgpu_encoder **out, nafgpu_error *err);
@@ -363,7 +370,7 @@ int nafgpu_encoder_set_device(nafgpu_encoder *enc, int device);
 
 /* The way back from nafgpu_decode_all_device: records that are in HBM -> an archive, without a host push per record. */
 typedef struct {
-    const uint8_t *d_sequence;  uint64_t n_bases;        /* ASCII letters (DNA/RNA: upper-case IUPAC) or raw text */
+    const uint8_t *d_sequence;  uint64_t n_bases;        /* ASCII letters (DNA/RNA: upper-case IUPAC; opts->mask: lower case too) or raw text */
     const uint8_t *d_quality;   uint64_t n_quality;
     const uint64_t *d_record_end; uint64_t n_records;    /* inclusive prefix sums of record lengths */
     const uint8_t *d_ids;       uint64_t n_ids_bytes;    /* NUL-terminated, concatenated (as decode_all_device leaves them) */
@@ -372,8 +379,10 @@ typedef struct {
 /* The archive nafgpu_encoder_finish gives when the same records are pushed one by one, byte for byte (compression_level 1
  * or 2, else NAFGPU_E_INVALID_ARG).  The host encoder's checks in bulk: quality total != sequence total, or a last record
  * end that is not the total: NAFGPU_E_INVALID_LENGTH; ids / comments that are not n_records NUL-terminated strings:
- * NAFGPU_E_MISSING_FIELD; a letter the nucleotide table refuses (lower case included: no Mask section is written):
- * NAFGPU_E_INVALID_SEQUENCE.  On any error nothing is produced.  *bytes is malloc'ed: free it with nafgpu_encode_free. */
+ * NAFGPU_E_MISSING_FIELD; a letter the nucleotide table refuses (lower case included unless opts->mask is set; with it, a
+ * lower-case letter whose upper-case form is refused): NAFGPU_E_INVALID_SEQUENCE, the message names the first one.  With
+ * opts->mask the Mask section's bytes are made in HBM from the letters' case (k_enc_mask_*) and compressed like every
+ * other section.  On any error nothing is produced.  *bytes is malloc'ed: free it with nafgpu_encode_free. */
 int nafgpu_encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts *opts, int device,
                          uint8_t **bytes, uint64_t *n, nafgpu_error *err);
 void nafgpu_encode_free(uint8_t *bytes);

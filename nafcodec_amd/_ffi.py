@@ -84,7 +84,7 @@ class SynthArchive(Structure):
 
 class EncoderOpts(Structure):
     _fields_ = [("sequence_type", c_uint8), ("id", c_uint8), ("comment", c_uint8), ("sequence", c_uint8), ("quality", c_uint8),
-                ("reserved", c_uint8 * 3), ("compression_level", ctypes.c_int32), ("threads", c_uint32)]
+                ("mask", c_uint8), ("reserved", c_uint8 * 2), ("compression_level", ctypes.c_int32), ("threads", c_uint32)]
 
 
 class EncodeSource(Structure):

@@ -231,6 +231,8 @@ int fail_c(nafgpu_error *err, const Failure &f) {
 
 Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts *opts, int device, std::vector<uint8_t> &o) {
     if (opts->sequence_type > 3) return Failure::make(NAFGPU_E_INVALID_ARG, "invalid encoder options");
+    if (!mask_opts_ok(*opts))
+        return Failure::make(NAFGPU_E_INVALID_ARG, "mask needs a nucleotide sequence: sequence set, sequence_type dna or rna");
     if (opts->compression_level != 1 && opts->compression_level != 2)
         return Failure::make(NAFGPU_E_INVALID_ARG, "the device encoder writes literal-only blocks: compression_level 1 or 2");
     if ((opts->id != 0) != (src->d_ids != nullptr) || (opts->comment != 0) != (src->d_comments != nullptr) ||
@@ -248,7 +250,7 @@ Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts
     const bool nuc = opts->sequence_type <= 1;
 
     // ---- every check first, as nafgpu_encoder_push does record by record
-    DevBuf d_tmp, d_totals, d_status, d_dummy, d_counts, d_offsets, d_words, d_packed;
+    DevBuf d_tmp, d_totals, d_status, d_dummy, d_counts, d_offsets, d_words, d_packed, d_mask;
     const uint32_t status0[4] = {0, 0, 0, 0};
     if (!d_tmp.alloc(scan_tmp_bytes(std::max<uint64_t>({n_rec, src->n_ids_bytes, src->n_comments_bytes, 1}))) ||
         !d_totals.alloc(sizeof(ScanTotals)) || !d_status.alloc(sizeof status0) || !d_dummy.alloc(16))
@@ -280,7 +282,7 @@ Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts
     if (opts->sequence && nuc) {
         uint32_t status[4] = {0, 0, 0, 0};
         if (!d_packed.alloc((src->n_bases + 1) / 2 + 16) || !reset_status()) return device_failure("out of device memory");
-        launch_enc_pack(stream, src->d_sequence, src->n_bases, opts->sequence_type, d_packed.bytes(), d_status.as<uint32_t>());
+        launch_enc_pack(stream, src->d_sequence, src->n_bases, opts->sequence_type, opts->mask != 0, d_packed.bytes(), d_status.as<uint32_t>());
         if (hipGetLastError() != hipSuccess || hipMemcpyAsync(status, d_status.bytes(), sizeof status, hipMemcpyDeviceToHost, stream) != hipSuccess ||
             hipStreamSynchronize(stream) != hipSuccess)
             return device_failure("packing the sequence failed");
@@ -305,6 +307,36 @@ Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts
         launch_enc_length_words(stream, src->d_record_end, n_rec, d_offsets.as<uint64_t>(), d_words.as<uint32_t>());
         if (hipGetLastError() != hipSuccess) return device_failure("the length pass failed");
     }
+    // ---- the Mask section: edges per tile, their offsets, the edge positions; bytes per unit, their offsets, the bytes.
+    // Two round trips: the host allocates by the number of edges, then by the number of bytes.
+    uint64_t n_mask = 0;
+    if (opts->mask && src->n_bases) {
+        const uint64_t n = src->n_bases, n_tiles = enc_mask_tiles(n);
+        DevBuf d_tile, d_mtmp, d_ends, d_sizes;                 // gone before the sections are compressed
+        ScanTotals tot{0, 0};
+        auto totals = [&]() {
+            return hipGetLastError() == hipSuccess && hipMemcpyAsync(&tot, d_totals.bytes(), sizeof tot, hipMemcpyDeviceToHost, stream) == hipSuccess &&
+                   hipStreamSynchronize(stream) == hipSuccess;
+        };
+        if (!d_tile.alloc_items(n_tiles, 8) || !d_mtmp.alloc(scan_tmp_bytes(n_tiles)) || !reset_status()) return device_failure("out of device memory");
+        launch_enc_mask_count(stream, src->d_sequence, n, d_tile.as<uint64_t>());
+        launch_scan_excl_u64(stream, d_tile.as<uint64_t>(), n_tiles, d_tile.as<uint64_t>(), d_mtmp.bytes(), d_totals.as<ScanTotals>(),
+                             d_status.as<uint32_t>());        // in place: a lane of k_scan_emit has read its items before it writes them
+        if (!totals()) return device_failure("the mask pass failed");
+        const uint64_t n_edges = tot.sum, n_units = n_edges + 1;
+        if (!d_ends.alloc_items(n_units, 8) || !d_sizes.alloc_items(n_units, 8) || !d_mtmp.alloc(scan_tmp_bytes(n_units)))
+            return device_failure("out of device memory");
+        launch_enc_mask_edges(stream, src->d_sequence, n, d_tile.as<uint64_t>(), n_edges, d_ends.as<uint64_t>());
+        launch_enc_mask_sizes(stream, d_ends.as<uint64_t>(), n_units, d_sizes.as<uint64_t>());
+        launch_scan_excl_u64(stream, d_sizes.as<uint64_t>(), n_units, d_sizes.as<uint64_t>(), d_mtmp.bytes(), d_totals.as<ScanTotals>(),
+                             d_status.as<uint32_t>());
+        if (!totals()) return device_failure("the mask pass failed");
+        n_mask = tot.sum;
+        if (!d_mask.alloc(n_mask)) return device_failure("out of device memory");
+        if (hipMemsetAsync(d_mask.bytes(), 0xFF, n_mask, stream) != hipSuccess) return device_failure("the mask pass failed");
+        launch_enc_mask_bytes(stream, d_ends.as<uint64_t>(), n_units, d_sizes.as<uint64_t>(), n_mask, d_mask.bytes());
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return device_failure("the mask pass failed");
+    }
     // ---- the container (Encoder::write, mod.rs:325-384)
     put_archive_head(o, *opts, n_rec);
     auto block = [&](const uint8_t *d_data, uint64_t n, uint64_t original) {
@@ -319,6 +351,7 @@ Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts
     if (opts->id) block(src->d_ids, src->n_ids_bytes, src->n_ids_bytes);
     if (opts->comment) block(src->d_comments, src->n_comments_bytes, src->n_comments_bytes);
     block(d_words.bytes(), n_words * 4, n_words * 4);
+    if (opts->mask) block(d_mask.bytes(), n_mask, n_mask);
     if (opts->sequence) {
         if (nuc) block(d_packed.bytes(), (src->n_bases + 1) / 2, src->n_bases);      // letters, not bytes
         else block(src->d_sequence, src->n_bases, src->n_bases);

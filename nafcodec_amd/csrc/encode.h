@@ -52,6 +52,8 @@ void compress_section(const std::vector<uint8_t> &data, unsigned n_threads, bool
 int nucleotide_code(uint8_t c, uint8_t sequence_type);
 void put_varint(std::vector<uint8_t> &out, uint64_t v);
 // header, flags, line length, record count: what stands in front of the sections (encoder/mod.rs:327-347)
+// opt.mask needs a nucleotide sequence (sequence set, DNA or RNA)
+bool mask_opts_ok(const nafgpu_encoder_opts &opt);
 void put_archive_head(std::vector<uint8_t> &out, const nafgpu_encoder_opts &opt, uint64_t n_records);
 
 // ---- the device path (encode.cpp) --------------------------------------------------------------
@@ -86,7 +88,21 @@ struct EncCopy {             // k_enc_scatter: `len` bytes to out + dst, from th
 };
 constexpr uint32_t kEncStBadLetter = 1, kEncStStreamSize = 2;    // status[0] bits; status[2..3]: u64, the complement of the first bad letter's index
 
-void launch_enc_pack(hipStream_t stream, const uint8_t *ascii, uint64_t n, uint8_t sequence_type, uint8_t *packed, uint32_t *status);
+// mask: a lower-case letter is packed as its upper-case form
+void launch_enc_pack(hipStream_t stream, const uint8_t *ascii, uint64_t n, uint8_t sequence_type, bool mask, uint8_t *packed,
+                     uint32_t *status);
+// The Mask section of n letters (encode.hip: k_enc_mask_*).  Edges: positions where the case changes (in front of letter 0:
+// upper case); n_edges + 1 units when n != 0.
+constexpr uint32_t kEncMaskTile = 4096;      // letters per workgroup of the two edge kernels (16 per lane)
+uint64_t enc_mask_tiles(uint64_t n);
+void launch_enc_mask_count(hipStream_t stream, const uint8_t *ascii, uint64_t n, uint64_t *tile_edges);       // enc_mask_tiles(n) counts
+// tile_first: the exclusive prefix sums of tile_edges; unit_end: n_edges + 1 entries, the last one n
+void launch_enc_mask_edges(hipStream_t stream, const uint8_t *ascii, uint64_t n, const uint64_t *tile_first, uint64_t n_edges,
+                           uint64_t *unit_end);
+void launch_enc_mask_sizes(hipStream_t stream, const uint64_t *unit_end, uint64_t n_units, uint64_t *sizes);  // bytes per unit
+// offsets: the exclusive prefix sums of sizes, n_bytes their total; `section` holds n_bytes bytes 0xFF already
+void launch_enc_mask_bytes(hipStream_t stream, const uint64_t *unit_end, uint64_t n_units, const uint64_t *offsets, uint64_t n_bytes,
+                           uint8_t *section);
 void launch_enc_length_counts(hipStream_t stream, const uint64_t *rec_end, uint64_t n_rec, uint64_t *counts);
 void launch_enc_length_words(hipStream_t stream, const uint64_t *rec_end, uint64_t n_rec, const uint64_t *offsets, uint32_t *words);
 void launch_enc_hist(hipStream_t stream, const uint8_t *src, uint64_t n, uint32_t n_blocks, uint32_t *hist);

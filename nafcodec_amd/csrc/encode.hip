@@ -1,6 +1,7 @@
 // encode.hip -- gfx950 (CDNA4, wave64) kernels of the encode path: literal-only Zstandard sections.
 //
 //   k_enc_pack      ASCII nucleotides -> 4-bit codes, two per byte (SequenceWriter, writer.rs:31-93)
+//   k_enc_mask_*    the letters' case -> the Mask section's bytes (the inverse of MaskReader, reader.rs:198-231)
 //   k_enc_length_*  record ends -> the Length section's 32-bit words (write_length, encoder/mod.rs:37-44)
 //   k_enc_hist      per 128 KiB block: symbol counts of its four Huffman streams
 //   k_enc_streams   one workgroup per stream: the backward bit stream, built in LDS, stored to its place in the frame
@@ -11,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "encode.h"
+#include "kernels.h"
 #include "plan.h"
 
 namespace nafgpu {
@@ -52,11 +54,14 @@ constexpr uint32_t kPackThreads = 256;
 
 // 16 letters -> 8 bytes per lane and step, the first letter of a pair in the low nibble.  The packing runs over the whole
 // section (record boundaries do not show); an odd total leaves a last byte with its high nibble zero.
+// MASK: a lower-case letter has the code of its upper-case form (the table's entries 'a'..'z' are those of 'A'..'Z');
+// its case goes to the Mask section (k_enc_mask_*).  Nothing but the table differs between the two forms.
+template <bool MASK>
 __global__ __launch_bounds__(kPackThreads) void k_enc_pack(const uint8_t *ascii, uint64_t n, uint32_t sequence_type, uint8_t *packed,
                                                             uint32_t *status) {
     __shared__ uint32_t s_lut[256];
     const uint32_t tid = threadIdx.x;
-    s_lut[tid] = enc_nuc(tid, sequence_type);
+    s_lut[tid] = enc_nuc(MASK && tid >= 'a' && tid <= 'z' ? tid - 32u : tid, sequence_type);
     __syncthreads();
     const uint64_t n_groups = (n + 15) / 16;
     const bool aligned = low4(ascii) == 0;
@@ -95,6 +100,102 @@ __global__ __launch_bounds__(kPackThreads) void k_enc_pack(const uint8_t *ascii,
             const uint32_t nb = (cnt + 1) / 2;
             for (uint32_t k = 0; k < nb; k++) d[k] = static_cast<uint8_t>((k < 4 ? lo >> (8u * k) : hi >> (8u * (k - 4))) & 0xFFu);
         }
+    }
+}
+
+// ======================================================================================
+// k_enc_mask_count / k_enc_mask_edges / k_enc_mask_sizes / k_enc_mask_bytes
+// ======================================================================================
+// The Mask section from the case of the letters.  masked(c) = 'a' <= c <= 'z'.  Letter i is an EDGE when masked(letter i)
+// != masked(letter i - 1), with masked(letter -1) = false; the units of the section are what lies between edges: unit k
+// spans [edge k-1, edge k), with edge -1 = 0 and the last unit ending at n, so that the first unit is an unmasked one (of
+// length 0 when letter 0 is lower case).  A lane takes 16 letters as one 16-bit case word w; its edges are
+// w ^ (w << 1 | case of the letter in front), which it reads from memory (the lane, the tile or the 16-byte load in front
+// may hold it).  Positions are 64-bit.
+//   count : edges per tile of kEncMaskTile letters                 (the caller scans them: launch_scan_excl_u64)
+//   edges : unit_end[k] = position of edge k, rank within the tile by a workgroup scan; unit_end[n_edges] = n
+//   sizes : bytes of unit k = length / 255 + 1                       (the caller scans them in place)
+//   bytes : the section is filled with 0xFF beforehand; unit k's last byte = length % 255
+// No lane loops over a unit's length: one unit of a genome without lower case is megabytes of 0xFF.
+constexpr uint32_t kMaskThreads = 256;
+static_assert(kEncMaskTile == kMaskThreads * 16, "a lane takes 16 letters");
+
+__device__ inline uint32_t masked_letter(uint32_t c) { return c - 'a' < 26u; }
+
+// the edges among letters [16 g, 16 g + 16) of the n letters, bit k = letter 16 g + k; letters from n on have none
+__device__ inline uint32_t mask_edges16(const uint8_t *ascii, uint64_t n, uint64_t g, bool aligned) {
+    const uint64_t o = 16 * g;
+    if (o >= n) return 0;
+    const uint32_t cnt = n - o < 16 ? static_cast<uint32_t>(n - o) : 16u;
+    uint32_t w[4] = {0, 0, 0, 0};
+    if (cnt == 16 && aligned) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(ascii + o);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++)
+            if (k < cnt) w[k >> 2] |= static_cast<uint32_t>(ascii[o + k]) << (8u * (k & 3u));
+    }
+    uint32_t cw = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++) cw |= masked_letter(byte_of(w, k)) << k;
+    const uint32_t before = o ? masked_letter(ascii[o - 1]) : 0u;
+    return (cw ^ ((cw << 1) | before)) & (0xFFFFu >> (16u - cnt));
+}
+
+// exclusive scan of one count per lane over the workgroup; *total: the sum
+__device__ inline uint32_t mask_scan(uint32_t v, uint32_t *s, uint32_t *total) {
+    const uint32_t t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (uint32_t d = 1; d < kMaskThreads; d <<= 1) {
+        const uint32_t a = t >= d ? s[t - d] : 0u;
+        __syncthreads();
+        s[t] += a;
+        __syncthreads();
+    }
+    *total = s[kMaskThreads - 1];
+    const uint32_t incl = s[t];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(kMaskThreads) void k_enc_mask_count(const uint8_t *ascii, uint64_t n, uint64_t *tile_edges) {
+    __shared__ uint32_t s_cnt[kMaskThreads];
+    const uint32_t e = mask_edges16(ascii, n, static_cast<uint64_t>(blockIdx.x) * kMaskThreads + threadIdx.x, low4(ascii) == 0);
+    uint32_t total;
+    (void)mask_scan(static_cast<uint32_t>(__builtin_popcount(e)), s_cnt, &total);
+    if (threadIdx.x == 0) tile_edges[blockIdx.x] = total;
+}
+
+// tile_first[t]: edges in front of tile t.  Nothing is stored at or behind unit_end[n_edges] but the closing n: letters
+// that changed between the two passes cannot make a store leave the array.
+__global__ __launch_bounds__(kMaskThreads) void k_enc_mask_edges(const uint8_t *ascii, uint64_t n, const uint64_t *tile_first, uint64_t n_edges,
+                                                                  uint64_t *unit_end) {
+    __shared__ uint32_t s_cnt[kMaskThreads];
+    const uint64_t g = static_cast<uint64_t>(blockIdx.x) * kMaskThreads + threadIdx.x;
+    uint32_t e = mask_edges16(ascii, n, g, low4(ascii) == 0);
+    uint32_t total;
+    uint64_t at = tile_first[blockIdx.x] + mask_scan(static_cast<uint32_t>(__builtin_popcount(e)), s_cnt, &total);
+    while (e) {                                              // at most 16 rounds
+        const uint32_t k = static_cast<uint32_t>(__builtin_ctz(e));
+        e &= e - 1;
+        if (at < n_edges) unit_end[at] = 16 * g + k;
+        at++;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) unit_end[n_edges] = n;
+}
+
+__global__ __launch_bounds__(256) void k_enc_mask_sizes(const uint64_t *unit_end, uint64_t n_units, uint64_t *sizes) {
+    for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x; k < n_units; k += static_cast<uint64_t>(gridDim.x) * 256)
+        sizes[k] = (unit_end[k] - (k ? unit_end[k - 1] : 0)) / 255 + 1;
+}
+
+__global__ __launch_bounds__(256) void k_enc_mask_bytes(const uint64_t *unit_end, uint64_t n_units, const uint64_t *offsets, uint64_t n_bytes,
+                                                         uint8_t *section) {
+    for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x; k < n_units; k += static_cast<uint64_t>(gridDim.x) * 256) {
+        const uint64_t behind = k + 1 < n_units ? offsets[k + 1] : n_bytes;
+        if (behind - 1 < n_bytes) section[behind - 1] = static_cast<uint8_t>((unit_end[k] - (k ? unit_end[k - 1] : 0)) % 255);
     }
 }
 
@@ -320,10 +421,40 @@ uint32_t grid_for(uint64_t items, uint32_t per_block) {
 
 }  // namespace
 
-void launch_enc_pack(hipStream_t stream, const uint8_t *ascii, uint64_t n, uint8_t sequence_type, uint8_t *packed, uint32_t *status) {
+void launch_enc_pack(hipStream_t stream, const uint8_t *ascii, uint64_t n, uint8_t sequence_type, bool mask, uint8_t *packed,
+                     uint32_t *status) {
     if (!n) return;
-    hipLaunchKernelGGL(k_enc_pack, dim3(grid_for((n + 15) / 16, kPackThreads)), dim3(kPackThreads), 0, stream, ascii, n,
-                       static_cast<uint32_t>(sequence_type), packed, status);
+    if (mask)
+        hipLaunchKernelGGL(k_enc_pack<true>, dim3(grid_for((n + 15) / 16, kPackThreads)), dim3(kPackThreads), 0, stream, ascii, n,
+                           static_cast<uint32_t>(sequence_type), packed, status);
+    else
+        hipLaunchKernelGGL(k_enc_pack<false>, dim3(grid_for((n + 15) / 16, kPackThreads)), dim3(kPackThreads), 0, stream, ascii, n,
+                           static_cast<uint32_t>(sequence_type), packed, status);
+}
+
+uint64_t enc_mask_tiles(uint64_t n) { return (n + kEncMaskTile - 1) / kEncMaskTile; }
+
+void launch_enc_mask_count(hipStream_t stream, const uint8_t *ascii, uint64_t n, uint64_t *tile_edges) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_enc_mask_count, dim3(static_cast<uint32_t>(enc_mask_tiles(n))), dim3(kMaskThreads), 0, stream, ascii, n, tile_edges);
+}
+
+void launch_enc_mask_edges(hipStream_t stream, const uint8_t *ascii, uint64_t n, const uint64_t *tile_first, uint64_t n_edges,
+                           uint64_t *unit_end) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_enc_mask_edges, dim3(static_cast<uint32_t>(enc_mask_tiles(n))), dim3(kMaskThreads), 0, stream, ascii, n, tile_first,
+                       n_edges, unit_end);
+}
+
+void launch_enc_mask_sizes(hipStream_t stream, const uint64_t *unit_end, uint64_t n_units, uint64_t *sizes) {
+    if (!n_units) return;
+    hipLaunchKernelGGL(k_enc_mask_sizes, dim3(grid_for(n_units, 256)), dim3(256), 0, stream, unit_end, n_units, sizes);
+}
+
+void launch_enc_mask_bytes(hipStream_t stream, const uint64_t *unit_end, uint64_t n_units, const uint64_t *offsets, uint64_t n_bytes,
+                           uint8_t *section) {
+    if (!n_units) return;
+    hipLaunchKernelGGL(k_enc_mask_bytes, dim3(grid_for(n_units, 256)), dim3(256), 0, stream, unit_end, n_units, offsets, n_bytes, section);
 }
 
 void launch_enc_length_counts(hipStream_t stream, const uint64_t *rec_end, uint64_t n_rec, uint64_t *counts) {

@@ -1066,6 +1066,8 @@ int nucleotide_code(uint8_t c, uint8_t sequence_type) {
     }
 }
 
+bool mask_opts_ok(const nafgpu_encoder_opts &opt) { return !opt.mask || (opt.sequence && opt.sequence_type <= 1); }
+
 void put_archive_head(std::vector<uint8_t> &o, const nafgpu_encoder_opts &opt, uint64_t n_records) {
     o.insert(o.end(), {0x01, 0xF9, 0xEC});                                           // mod.rs:327
     uint8_t flags = 0;                                                               // mod.rs:176-193
@@ -1073,6 +1075,7 @@ void put_archive_head(std::vector<uint8_t> &o, const nafgpu_encoder_opts &opt, u
     if (opt.comment) flags |= 0x10;
     if (opt.sequence) flags |= 0x02 | 0x08;
     if (opt.quality) flags |= 0x01 | 0x08;
+    if (opt.mask) flags |= 0x04;
     if (opt.sequence_type == 0) {                                                    // V1 for DNA, V2 else (mod.rs:169-173, 329-342)
         o.insert(o.end(), {0x01, flags, ' '});
     } else {
@@ -1097,6 +1100,16 @@ void put_length_words(std::vector<uint8_t> &out, uint64_t l) {   // write_length
     word(static_cast<uint32_t>(l));
 }
 
+// one unit of the Mask section, the inverse of MaskReader (reader.rs:198-231): a byte other than 0xFF ends the unit
+void put_mask_unit(std::vector<uint8_t> &out, uint64_t l) {
+    out.insert(out.end(), l / 255, 0xFF);
+    out.push_back(static_cast<uint8_t>(l % 255));
+}
+
+inline bool masked_letter(uint8_t c) { return c >= 'a' && c <= 'z'; }
+// opt.mask: a lower-case letter is packed as its upper-case form
+inline uint8_t fold_letter(uint8_t c, bool mask) { return mask && masked_letter(c) ? static_cast<uint8_t>(c - 32) : c; }
+
 int enc_fail(nafgpu_error *err, int status, const char *msg) {
     if (err) {
         std::memset(err, 0, sizeof *err);
@@ -1111,6 +1124,9 @@ int enc_fail(nafgpu_error *err, int status, const char *msg) {
 struct nafgpu_encoder {
     nafgpu_encoder_opts opt{};
     std::vector<uint8_t> ids, coms, lens, seq, qual;   // section contents, uncompressed (Memory storage: storage.rs)
+    std::vector<uint8_t> mask;                          // opt.mask: the Mask section's closed units
+    uint64_t unit_len = 0;                              // the open unit (it runs on across records): its length so far
+    bool unit_masked = false;                           // and its case; the first unit is an unmasked one
     uint64_t seq_letters = 0;                           // what the reference's WriteCounter counts for the sequence: letters
     int cache = -1;                                     // a nucleotide waiting for its partner (writer.rs:9,69-77)
     uint64_t n_records = 0;
@@ -1136,6 +1152,8 @@ extern "C" void nafgpu_encoder_opts_from_flags(uint8_t sequence_type, uint8_t fl
 
 extern "C" int nafgpu_encoder_new(const nafgpu_encoder_opts *opts, nafgpu_encoder **out, nafgpu_error *err) {
     if (!opts || !out || opts->sequence_type > 3) return enc_fail(err, NAFGPU_E_INVALID_ARG, "invalid encoder options");
+    if (!nafgpu::enc::mask_opts_ok(*opts))
+        return enc_fail(err, NAFGPU_E_INVALID_ARG, "mask needs a nucleotide sequence: sequence set, sequence_type dna or rna");
     nafgpu_encoder *e = new (std::nothrow) nafgpu_encoder();
     if (!e) return enc_fail(err, NAFGPU_E_IO, "out of memory");
     e->opt = *opts;
@@ -1146,7 +1164,7 @@ extern "C" int nafgpu_encoder_new(const nafgpu_encoder_opts *opts, nafgpu_encode
 extern "C" int nafgpu_encoder_push(nafgpu_encoder *e, const nafgpu_record *r, nafgpu_error *err) {
     if (!e || !r) return enc_fail(err, NAFGPU_E_INVALID_ARG, "null argument");
     if (e->finished) return enc_fail(err, NAFGPU_E_INVALID_ARG, "the archive has been written already");
-    const bool nuc = e->opt.sequence_type <= 1;
+    const bool nuc = e->opt.sequence_type <= 1, mask = e->opt.mask != 0;
     // ---- every check first (mod.rs:236-317 checks field by field, writing as it goes)
     if (e->opt.id && !r->id.present) return enc_fail(err, NAFGPU_E_MISSING_FIELD, "missing record field: \"id\"");
     if (e->opt.comment && !r->comment.present) return enc_fail(err, NAFGPU_E_MISSING_FIELD, "missing record field: \"comment\"");
@@ -1155,7 +1173,7 @@ extern "C" int nafgpu_encoder_push(nafgpu_encoder *e, const nafgpu_record *r, na
         return enc_fail(err, NAFGPU_E_INVALID_LENGTH, "inconsistent sequence length");
     if (e->opt.sequence && nuc)
         for (uint64_t i = 0; i < r->sequence.len; i++)
-            if (nucleotide_code(r->sequence.ptr[i], e->opt.sequence_type) < 0)
+            if (nucleotide_code(fold_letter(r->sequence.ptr[i], mask), e->opt.sequence_type) < 0)
                 return enc_fail(err, NAFGPU_E_INVALID_SEQUENCE, "invalid character in sequence");
     if (e->opt.quality && !r->quality.present) return enc_fail(err, NAFGPU_E_MISSING_FIELD, "missing record field: \"quality\"");
     bool have_len = r->has_length != 0;
@@ -1184,19 +1202,29 @@ extern "C" int nafgpu_encoder_push(nafgpu_encoder *e, const nafgpu_record *r, na
         const uint8_t *s = r->sequence.ptr;
         uint64_t n = r->sequence.len;
         e->seq_letters += n;
+        if (mask)                                                                    // the units run over the concatenated letters
+            for (uint64_t i = 0; i < n; i++) {
+                const bool m = masked_letter(s[i]);
+                if (m != e->unit_masked) {
+                    put_mask_unit(e->mask, e->unit_len);
+                    e->unit_len = 0;
+                    e->unit_masked = m;
+                }
+                e->unit_len++;
+            }
+        auto code = [&](uint8_t c) { return nucleotide_code(fold_letter(c, mask), e->opt.sequence_type); };
         if (!nuc) {
             e->seq.insert(e->seq.end(), s, s + n);
         } else if (n) {                                                              // writer.rs:60-93: two letters per byte, first in the low nibble
             if (e->cache >= 0) {
-                e->seq.push_back(static_cast<uint8_t>((nucleotide_code(s[0], e->opt.sequence_type) << 4) | e->cache));
+                e->seq.push_back(static_cast<uint8_t>((code(s[0]) << 4) | e->cache));
                 e->cache = -1;
                 s++;
                 n--;
             }
             for (uint64_t i = 0; i + 1 < n; i += 2)
-                e->seq.push_back(static_cast<uint8_t>((nucleotide_code(s[i + 1], e->opt.sequence_type) << 4) |
-                                                      nucleotide_code(s[i], e->opt.sequence_type)));
-            if (n & 1) e->cache = nucleotide_code(s[n - 1], e->opt.sequence_type);
+                e->seq.push_back(static_cast<uint8_t>((code(s[i + 1]) << 4) | code(s[i])));
+            if (n & 1) e->cache = code(s[n - 1]);
         }
     }
     if (e->opt.quality) {
@@ -1214,6 +1242,8 @@ extern "C" int nafgpu_encoder_finish(nafgpu_encoder *e, const uint8_t **bytes, u
             e->seq.push_back(static_cast<uint8_t>(e->cache));
             e->cache = -1;
         }
+        const size_t mask_closed = e->mask.size();
+        if (e->opt.mask && e->seq_letters) put_mask_unit(e->mask, e->unit_len);      // the open unit ends with the last letter; no letters: no units
         std::vector<uint8_t> &o = e->archive;
         put_archive_head(o, e->opt, e->n_records);
         nafgpu::Failure dev_fail;
@@ -1232,10 +1262,12 @@ extern "C" int nafgpu_encoder_finish(nafgpu_encoder *e, const uint8_t **bytes, u
         if (e->opt.id) block(e->ids, e->ids.size());
         if (e->opt.comment) block(e->coms, e->coms.size());
         block(e->lens, e->lens.size());                                              // always, whatever the flags say (mod.rs:371)
+        if (e->opt.mask) block(e->mask, e->mask.size());                             // between Length and Sequence, even when empty
         if (e->opt.sequence) block(e->seq, e->seq_letters);                          // letters, not bytes (the counter wraps the SequenceWriter)
         if (e->opt.quality) block(e->qual, e->qual.size());
         if (!dev_fail.ok()) {                                                        // nothing is written; the sections stay for another try
             o.clear();
+            e->mask.resize(mask_closed);                                             // the open unit stays open
             dev_fail.to_c(err);
             return dev_fail.status;
         }
@@ -1243,6 +1275,7 @@ extern "C" int nafgpu_encoder_finish(nafgpu_encoder *e, const uint8_t **bytes, u
         std::vector<uint8_t>().swap(e->ids);
         std::vector<uint8_t>().swap(e->coms);
         std::vector<uint8_t>().swap(e->lens);
+        std::vector<uint8_t>().swap(e->mask);
         std::vector<uint8_t>().swap(e->seq);
         std::vector<uint8_t>().swap(e->qual);
     }

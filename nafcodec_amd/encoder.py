@@ -2,7 +2,8 @@
 (nafcodec-py/nafcodec/lib.pyi:69-87, lib.rs:463-600; the Rust side: encoder/mod.rs:46-384).  Host code, like the
 reference's; every section is written as Huffman-literal Zstandard blocks (include/nafgpu.h: Encoder).  With `device=` the
 sections of compression levels 1 and 2 are compressed by the HIP kernels instead (same bytes), and `encode_device` writes
-an archive from records that are already in HBM."""
+an archive from records that are already in HBM.  `mask=True` (no counterpart in the reference, whose mask writer is
+commented out) accepts lower-case nucleotides and writes their runs as a Mask section."""
 import ctypes
 import os
 from ctypes import byref, c_uint64, c_void_p
@@ -15,9 +16,10 @@ class Encoder:
     """lib.pyi:69-87.  `file` is a path or a binary file-like object; the archive is written by close()."""
 
     def __init__(self, file, sequence_type="dna", *, id=False, comment=False, sequence=False, quality=False,
-                 compression_level=0, device=None, _lib=None):
+                 compression_level=0, device=None, mask=False, _lib=None):
         if sequence_type not in SEQUENCE_TYPES:
             raise ValueError("expected 'dna', 'rna', 'protein' or 'text', got %r" % (sequence_type,))   # lib.rs:487-495
+        _check_mask(mask, sequence_type, sequence)
         self._lib = _lib or _ffi.default()
         self._file = file
         self._h = None
@@ -26,7 +28,7 @@ class Encoder:
         opts = _ffi.EncoderOpts()
         self._lib.c.nafgpu_encoder_opts_default(SEQUENCE_TYPES.index(sequence_type), byref(opts))
         opts.id, opts.comment, opts.sequence, opts.quality = map(int, (id, comment, sequence, quality))
-        opts.compression_level = int(compression_level)
+        opts.compression_level, opts.mask = int(compression_level), int(bool(mask))
         h, err = c_void_p(), _ffi.Error()
         if self._lib.c.nafgpu_encoder_new(byref(opts), byref(h), byref(err)) != _ffi.OK:
             raise _ffi.NafError.from_c(err)
@@ -108,19 +110,26 @@ def zstd_compress(data, device=0, _lib=None):
     return (_lib or _ffi.default()).zstd_compress(bytes(data), device)
 
 
+def _check_mask(mask, sequence_type, sequence):
+    if mask and (sequence_type not in ("dna", "rna") or not sequence):
+        raise ValueError("mask=True needs a nucleotide sequence: sequence=True and sequence_type 'dna' or 'rna'")
+
+
 def encode_device(result, *, sequence_type="dna", id=False, comment=False, sequence=False, quality=False, compression_level=1,
-                  device=None, threads=0, _lib=None):
+                  device=None, threads=0, mask=False, _lib=None):
     """Records in HBM -> an archive (bytes), equal to what Encoder writes when the same records are pushed one by one.
     `result` is what Decoder.decode_all_device() returns, or anything with its fields (d_sequence / n_bases, d_quality /
     n_quality, d_record_end / n_records, d_ids / n_ids_bytes, d_comments / n_comments_bytes) holding device addresses --
-    a torch tensor's data_ptr() will do.  Only the enabled fields are read."""
+    a torch tensor's data_ptr() will do.  Only the enabled fields are read.  `mask=True`: the letters may be lower case, as
+    decode_all_device() leaves them; the Mask section is made from their case on the device."""
     if sequence_type not in SEQUENCE_TYPES:
         raise ValueError("expected 'dna', 'rna', 'protein' or 'text', got %r" % (sequence_type,))
+    _check_mask(mask, sequence_type, sequence)
     lib = _lib or _ffi.default()
     opts = _ffi.EncoderOpts()
     lib.c.nafgpu_encoder_opts_default(SEQUENCE_TYPES.index(sequence_type), byref(opts))
     opts.id, opts.comment, opts.sequence, opts.quality = map(int, (id, comment, sequence, quality))
-    opts.compression_level, opts.threads = int(compression_level), int(threads)
+    opts.compression_level, opts.threads, opts.mask = int(compression_level), int(threads), int(bool(mask))
     src = _ffi.EncodeSource()
     src.n_records, src.d_record_end = int(result.n_records), result.d_record_end
     if id:
