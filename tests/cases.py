@@ -403,22 +403,119 @@ def check_next_batch(blob, opts=None, lib=None, caps=(1, 3, 64, 4096)):
     return len(want)
 
 
-def check_archive_ends(lib, n_bases, seed, n_blk):
+def raw_frame(data):
+    """`data` as one magicless zstd frame of raw blocks (FHD 0, window 512 KiB, blocks of up to 128 KiB): what the synthetic
+    writer uses for its small sections, and nothing a compressor has to be trusted for"""
+    data = bytes(data)
+    out, pos = bytearray(b"\x00\x48"), 0
+    while True:
+        n = min(131072, len(data) - pos)
+        last = pos + n == len(data)
+        out += ((n << 3) | int(last)).to_bytes(3, "little") + data[pos:pos + n]
+        pos += n
+        if last:
+            return bytes(out)
+
+
+def mask_unit_ends(mask):
+    """decoded Mask section -> the units' ends in letters (numpy uint64), unit k masked when k is odd: a unit ends at a
+    byte != 0xFF and is as long as its bytes add up to (reader.rs:198-231)"""
+    a = np.frombuffer(mask, dtype=np.uint8)
+    assert len(a) == 0 or a[-1] != 0xFF, "the Mask section ends inside a unit"
+    return np.cumsum(a, dtype=np.uint64)[a != 0xFF]
+
+
+def mask_section_bytes(lengths):
+    """unit lengths (unmasked first) -> the Mask section's bytes, l // 255 times FF and then l % 255 for each unit, without
+    a Python loop per unit or per 255 letters (tests/naf_writer.py: mask_bytes has those)"""
+    lengths = np.asarray(lengths, dtype=np.uint64)
+    if not len(lengths):
+        return b""
+    counts = (lengths // np.uint64(255) + np.uint64(1)).astype(np.int64)
+    out = np.full(int(counts.sum()), 0xFF, dtype=np.uint8)
+    out[np.cumsum(counts) - 1] = (lengths % np.uint64(255)).astype(np.uint8)
+    return out.tobytes()
+
+
+def cut_units(ends, w0, w1):
+    """The units (their ends: mask_unit_ends) cut to the letters [w0, w1) -> unit lengths that start with an unmasked unit
+    and add up to w1 - w0 exactly: the first and the last unit clipped, the alternation kept -- a window that starts inside
+    a masked unit (an odd one) starts with an unmasked unit of length 0."""
+    assert 0 <= w0 < w1 <= int(ends[-1])
+    k0 = int(np.searchsorted(ends, np.uint64(w0), side="right"))          # the first unit that ends behind w0
+    k1 = int(np.searchsorted(ends, np.uint64(w1), side="left"))           # the first unit that reaches w1
+    cut = np.minimum(ends[k0:k1 + 1], np.uint64(w1))
+    lengths = np.diff(np.concatenate((np.array([w0], dtype=np.uint64), cut)))
+    if k0 & 1:
+        lengths = np.concatenate((np.zeros(1, dtype=np.uint64), lengths))
+    assert int(lengths.sum()) == w1 - w0
+    return lengths
+
+
+def masked_runs_touching_record_ends(unit_ends, record_ends):
+    """how many masked units [s, e) with letters hold a record end r with s < r <= e: the ones the reference's decoder
+    leaves partly in upper case (oracle/naf_oracle.c: mask_sequence) -- for all others its reading and the
+    specification's are the same"""
+    starts = np.concatenate((np.zeros(1, dtype=np.uint64), unit_ends[:-1]))
+    s, e = starts[1::2], unit_ends[1::2]
+    s, e = s[e > s], e[e > s]
+    record_ends = np.asarray(record_ends, dtype=np.uint64)
+    nxt = np.searchsorted(record_ends, s, side="right")                   # the first record end behind s
+    hit = nxt < len(record_ends)
+    return int((record_ends[nxt[hit]] <= e[hit]).sum()), len(s)
+
+
+def check_synth_mask_premise(lib, n_bases, seed):
+    """The synthetic writer keeps its masked runs strictly inside records, so the reference's default reading of such an
+    archive and the specification's are the same text: asserted on the Mask section's unit ends against the record ends the
+    oracle reports, not assumed (check_archive_ends(with_mask=True) reads the full archive with the default)."""
+    import ctypes
+    from nafcodec_amd import _ffi
+    from oracle import oracle
+    L = lib or _ffi.default()
+    arc = L.synth(n_bases, seed=seed, with_mask=True)
+    try:
+        blob = ctypes.string_at(arc.bytes, arc.n)
+    finally:
+        L.c.nafgpu_synth_free(ctypes.byref(arc))
+    ends = np.cumsum([r[4] for r in run_oracle(blob, {"sequence": False, "mask": False})[0]], dtype=np.uint64)
+    units = mask_unit_ends(oracle.Decoder(blob).section(3)[0])
+    assert int(ends[-1]) == int(units[-1]) == n_bases
+    touching, masked = masked_runs_touching_record_ends(units, ends)
+    assert touching == 0 and masked > n_bases // 10000, (touching, masked)
+    assert oracle.Decoder(blob).drain().seq_hash == oracle.Decoder(blob, spec_mask=True).drain().seq_hash
+    # ... and the helper does see a run that reaches a record's end, or crosses one
+    assert masked_runs_touching_record_ends(np.array([5, 10, 30], dtype=np.uint64), [10, 30])[0] == 1
+    assert masked_runs_touching_record_ends(np.array([5, 12, 30], dtype=np.uint64), [10, 30])[0] == 1
+    assert masked_runs_touching_record_ends(np.array([10, 12, 30], dtype=np.uint64), [10, 30])[0] == 0
+    return masked
+
+
+def check_archive_ends(lib, n_bases, seed, n_blk, with_mask=False):
     """A synthetic DNA-only archive of any size: its first and its last `n_blk` zstd blocks (the tail cut at one of the
     writer's 64-block units, where a block brings its own Huffman tree) are re-framed as small archives of ONE record each,
     the CPU oracle decodes those, and the bytes the product wrote for the WHOLE archive at those positions must be the
     same -- so that a full-size decode (positions beyond 2^35 for the tail of the 40-Gbase archive) is not only checked
-    against the writer's own checksums.  The archive is opened by path (mapped, as bench.py's iterator leg does)."""
+    against the writer's own checksums.  The archive is opened by path (mapped, as bench.py's iterator leg does).
+
+    `with_mask`: the archive has a Mask section, and so have the small archives -- the full archive's units (its Mask frame
+    through the oracle's zstd decoder) cut to each window by cut_units.  The small archives hold ONE record, so a masked run
+    that the window's end cuts reaches that record's end, and the reference's default reading would leave it in upper case
+    (SURVEY App. D-1): the oracle reads the small archives with spec_mask=True.  The product reads the full archive with its
+    default; there the two readings agree, because the writer keeps masked runs strictly inside records
+    (check_synth_mask_premise asserts that).  Each window must hold lower-case letters.  -> (lower-case letters in the
+    first window, in the last)"""
     import ctypes
     import os
     import shutil
     import tempfile
     from nafcodec_amd import _ffi
+    import zstd_ref
     from nafcodec_amd.decoder import Decoder
     from oracle import oracle
     L = lib or _ffi.default()
     kw = {} if lib is None else {"_lib": lib}
-    arc = L.synth(n_bases, seed=seed)
+    arc = L.synth(n_bases, seed=seed, with_mask=with_mask)
     path = os.path.join("/dev/shm" if shutil.disk_usage("/dev/shm").free > 2 * arc.n else tempfile.gettempdir(), "nafgpu_ends_%d.naf" % os.getpid())
     try:
         mv = memoryview((ctypes.c_uint8 * arc.n).from_address(arc.bytes)).cast("B")
@@ -438,6 +535,18 @@ def check_archive_ends(lib, n_bases, seed, n_blk):
         n_rec = varint()
         _len_orig, len_comp = varint(), varint()
         at += len_comp
+        units = None
+        if with_mask:                                           # the Mask section sits between Length and Sequence (flag 0x04)
+            assert mv[4] == 0x0E
+            mask_orig, mask_comp = varint(), varint()
+            mask = oracle.zstd_decode(bytes(mv[at:at + mask_comp]), mask_orig + 8)
+            assert len(mask) == mask_orig
+            units = mask_unit_ends(mask)
+            del mask
+            assert int(units[-1]) == n_bases
+            at += mask_comp
+        else:
+            assert mv[4] == 0x0A
         assert varint() == n_bases
         seq_comp = varint()
         frame0, frame1 = at, at + seq_comp
@@ -454,14 +563,19 @@ def check_archive_ends(lib, n_bases, seed, n_blk):
         blk = 131072
         assert pos == frame1 and len(offs) == ((n_bases + 1) // 2 + blk - 1) // blk and len(offs) > n_blk
 
-        def small_archive(b0, b1, bases):
+        def small_archive(b0, b1, bases, base0=0):
             body = bytearray(mv[offs[b0]:(offs[b1] if b1 < len(offs) else frame1)])
             body[offs[b1 - 1] - offs[b0]] |= 1                  # the last block of the cut closes the frame
             frame = bytes(mv[frame0:frame0 + 2]) + bytes(body)
             lens = nw.length_words([bases])
             len_frame = bytes([0x20, len(lens), (len(lens) << 3) | 1, 0, 0]) + lens      # single-segment frame, one raw block
-            return (bytes([1, 0xF9, 0xEC, 1, 0x0A, 0x20]) + nw.varint(60) + nw.varint(1) + nw.varint(len(lens)) + nw.varint(len(len_frame)) +
-                    len_frame + nw.varint(bases) + nw.varint(len(frame)) + frame)
+            mask_section = b""
+            if with_mask:
+                mask = mask_section_bytes(cut_units(units, base0, base0 + bases))
+                mask_frame = zstd_ref.compress_magicless(mask, 1, True) if zstd_ref.available() else raw_frame(mask)
+                mask_section = nw.varint(len(mask)) + nw.varint(len(mask_frame)) + mask_frame
+            return (bytes([1, 0xF9, 0xEC, 1, 0x0E if with_mask else 0x0A, 0x20]) + nw.varint(60) + nw.varint(1) + nw.varint(len(lens)) +
+                    nw.varint(len(len_frame)) + len_frame + mask_section + nw.varint(bases) + nw.varint(len(frame)) + frame)
 
         with open(path, "wb") as f:
             f.write(mv)
@@ -470,13 +584,18 @@ def check_archive_ends(lib, n_bases, seed, n_blk):
         dec = Decoder(path, **kw)
         res = dec.decode_all_device()
         assert (res.n_bases, res.n_records) == (n_bases, arc.n_records) and n_rec == arc.n_records
+        lower = []
         for b0, b1, base0, n in ((0, n_blk, 0, n_blk * 2 * blk), (first_tail_blk, len(offs), tail_base, n_bases - tail_base)):
-            want = oracle.Decoder(small_archive(b0, b1, n)).drain()
+            want = oracle.Decoder(small_archive(b0, b1, n, base0), spec_mask=with_mask).drain()
             assert (want.n_bases, want.n_records) == (n, 1)
             got = dec.copy_to_host(res.d_sequence + base0, n)
             assert L.c.nafgpu_hash64_host(got, n) == want.seq_hash, (b0, b1)
+            lower.append(int((np.frombuffer(got, dtype=np.uint8) >= 97).sum()))
             del got
+            # a check that compares two unmasked texts proves nothing
+            assert (lower[-1] > 0) == with_mask, (b0, b1, lower)
         dec.close()
+        return tuple(lower)
     finally:
         L.c.nafgpu_synth_free(ctypes.byref(arc))
         if os.path.exists(path):

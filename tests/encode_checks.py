@@ -56,6 +56,27 @@ def sections(blob):
     return out
 
 
+def section_spans(blob):
+    """-> {name: (original_size, first byte, end) of the payload} without copying a payload (`blob`: bytes or a memoryview
+    over an archive of any size); "n_records" and "flags" beside them"""
+    assert bytes(blob[:3]) == b"\x01\xF9\xEC"
+    if blob[3] == 1:
+        flags, at = blob[4], 6
+    else:
+        flags, at = blob[5], 7
+    _, at = read_varint(blob, at)
+    out = {"flags": flags}
+    out["n_records"], at = read_varint(blob, at)
+    for name, bit in (("ids", 0x20), ("comments", 0x10), ("lengths", 0x08), ("mask", 0x04), ("sequence", 0x02), ("quality", 0x01)):
+        if flags & bit:
+            orig, at = read_varint(blob, at)
+            comp, at = read_varint(blob, at)
+            out[name] = (orig, at, at + comp)
+            at += comp
+    assert at == len(blob)
+    return out
+
+
 def host_archive(lib, records, sequence_type, level, device=None, **fields):
     buf = io.BytesIO()
     with Encoder(buf, sequence_type, compression_level=level, device=device, _lib=lib, **fields) as enc:
@@ -74,7 +95,7 @@ def host_frame(lib, data):
 
 def block_types(frame):
     """block by block: 'raw', 'rle', 'huf' (Huffman with a new tree), 'treeless'; anything else fails"""
-    assert frame[:2] == b"\x00\x48"
+    assert bytes(frame[:2]) == b"\x00\x48"                 # (`frame`: bytes or a memoryview)
     at, out = 2, []
     while True:
         bh = frame[at] | (frame[at + 1] << 8) | (frame[at + 2] << 16)
