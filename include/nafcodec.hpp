@@ -288,6 +288,21 @@ inline std::string encode_device(const nafgpu_encode_source &src, const EncoderB
     return out;
 }
 
+// (no counterpart in the reference; what `ennaf` does) FASTA / FASTQ text -> an archive, parsed and encoded on the GPU:
+// nafgpu_encode_text.  `fields` as for encode_device (quality needs FASTQ text); keep_line_length: the header carries the
+// text's longest sequence line instead of 60.  The format is told by the text's first byte.
+inline std::string encode_text(const std::string &text, const EncoderBuilder &fields, bool keep_line_length = true, int device = -1) {
+    uint8_t *p = nullptr;
+    uint64_t n = 0;
+    nafgpu_error err{};
+    if (nafgpu_encode_text(reinterpret_cast<const uint8_t *>(text.data()), text.size(), nullptr, &fields.options(), keep_line_length ? 1 : 0,
+                           device, &p, &n, &err) != NAFGPU_OK)
+        throw Error(err);
+    std::string out(reinterpret_cast<const char *>(p), n);
+    nafgpu_encode_free(p);
+    return out;
+}
+
 // (no counterpart in the reference: the library keeps device memory of closed decoders for the next one -- nafgpu.h)
 inline void trim_device_memory(int device = -1) { (void)nafgpu_trim_device_memory(device); }
 

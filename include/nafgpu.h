@@ -391,6 +391,52 @@ void nafgpu_encode_free(uint8_t *bytes);
  * (tools/encode_probe.py) */
 void nafgpu_encode_last_times(double *hist_ms, double *streams_ms, double *plan_ms, double *total_ms);
 
+/* ---- FASTA / FASTQ text -> records in HBM -> archive (what `ennaf` does; the inverse of nafgpu_format_device) ----
+ * The text is parsed by HIP kernels (parse.hip): no host loop over it, no array with an entry per line.  Rules, the
+ * inverse of the text rules at nafgpu_format_device with name_separator ' ':
+ *   lines    end at '\n'; the last one may lack it.  A '\r' directly in front of a '\n', or as the very last byte, goes
+ *            with it; any other '\r' is data.
+ *   format   0 = by the first byte ('>' FASTA, '@' FASTQ), 1 = FASTA, 2 = FASTQ.  Empty text: zero records.  Another first
+ *            byte, or one that disagrees with the stated format: NAFGPU_E_INVALID_ARG.
+ *   FASTA    a line that begins with '>' opens a record: id = the bytes behind '>' up to the first ' ', comment = all
+ *            behind that ' ' (empty when there is none); the sequence = the bytes of the lines up to the next such line,
+ *            line ends removed.  Empty lines add nothing; a '>' elsewhere in a line is data.
+ *   FASTQ    four lines per record, by line index mod 4: '@' id [' ' comment] / sequence / '+' anything / quality.  A line
+ *            count that is not a multiple of 4, a first line without '@', a third without '+': NAFGPU_E_INVALID_ARG, the
+ *            message names the byte offset of the first offending line (of the text's end for a missing line).  A quality
+ *            that is not as long as its sequence: NAFGPU_E_INVALID_LENGTH, the message names the first such record.
+ *   NUL      in a header line: NAFGPU_E_INVALID_ARG with its byte offset (ids and comments are NUL-terminated).
+ *   letters  are not judged here: the encode stage refuses them (NAFGPU_E_INVALID_SEQUENCE).
+ * line_length = the longest sequence line (without its '\r').  On any error nothing is produced. */
+typedef struct {
+    uint8_t format;              /* 0 auto, 1 FASTA, 2 FASTQ */
+    uint8_t text_on_device;      /* `text` is a device pointer: it is read where it lies */
+    uint8_t reserved[6];
+} nafgpu_parse_opts;
+typedef struct nafgpu_parsed nafgpu_parsed;     /* owns the device buffers of one parse */
+typedef struct {
+    nafgpu_encode_source src;    /* device pointers, valid until the parse is freed: feed it to nafgpu_encode_device as it is
+                                    (d_quality is NULL for FASTA) */
+    uint64_t line_length;        /* longest sequence line */
+    uint64_t n_text;
+    uint8_t fastq, reserved[3];
+    float ms;                    /* the parse kernels, HIP events */
+} nafgpu_parse_result;
+void nafgpu_parse_opts_default(nafgpu_parse_opts *opts);
+/* host text goes to the device first (staged); opts may be NULL (auto, host text); device -1 = current */
+int nafgpu_parse_text(const uint8_t *text, uint64_t n, const nafgpu_parse_opts *opts, int device,
+                      nafgpu_parsed **out, nafgpu_parse_result *res, nafgpu_error *err);
+int nafgpu_parse_copy_to_host(nafgpu_parsed *parsed, const void *d_ptr, uint64_t n, void *dst);
+/* checksum of a device buffer, equal to nafgpu_hash64_host of the same bytes */
+int nafgpu_parse_hash64(nafgpu_parsed *parsed, const void *d_ptr, uint64_t n, uint64_t *out);
+void nafgpu_parse_free(nafgpu_parsed *parsed);
+/* Parse and encode in one call.  With keep_line_length = 0 the archive is, byte for byte, what the host Encoder
+ * writes when the same records are pushed one by one; with 1 the header carries the text's line_length instead of 60 and
+ * nothing else differs.  compression_level 1 or 2; opts->quality with FASTA text: NAFGPU_E_MISSING_FIELD; opts->mask as
+ * for the encoders.  Fields of the text that opts does not name are dropped.  *bytes: free with nafgpu_encode_free. */
+int nafgpu_encode_text(const uint8_t *text, uint64_t n, const nafgpu_parse_opts *popts, const nafgpu_encoder_opts *opts,
+                       int keep_line_length, int device, uint8_t **bytes, uint64_t *n_out, nafgpu_error *err);
+
 /* order-sensitive 64-bit checksum used for full-size parity checks: sum over the 8-byte words w_j of
  * mix64(w_j ^ (j + 1) * K) -- every word is mixed non-linearly with its position before it is added, so
  * byte errors cannot cancel -- see hash64.h */

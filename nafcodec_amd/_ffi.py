@@ -94,6 +94,16 @@ class EncodeSource(Structure):
                 ("d_comments", c_void_p), ("n_comments_bytes", c_uint64)]
 
 
+class ParseOpts(Structure):
+    _fields_ = [("format", c_uint8), ("text_on_device", c_uint8), ("reserved", c_uint8 * 6)]
+
+
+class ParseResult(Structure):
+    """nafgpu_parse_result: `src` is what nafgpu_encode_device takes."""
+    _fields_ = [("src", EncodeSource), ("line_length", c_uint64), ("n_text", c_uint64), ("fastq", c_uint8), ("reserved", c_uint8 * 3),
+                ("ms", c_float)]
+
+
 READ_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, POINTER(c_uint8), c_uint64)
 SEEK_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, c_int64, c_int)
 
@@ -110,6 +120,8 @@ EXPORTS = [
     "nafgpu_hash64_host_at", "nafgpu_shard_begin", "nafgpu_shard_place", "nafgpu_shard_halo", "nafgpu_shard_export_tail",
     "nafgpu_shard_import_halo", "nafgpu_shard_finish", "nafgpu_next_batch", "nafgpu_trim_device_memory",
     "nafgpu_zstd_compress", "nafgpu_encoder_set_device", "nafgpu_encode_device", "nafgpu_encode_free", "nafgpu_encode_last_times",
+    "nafgpu_parse_opts_default", "nafgpu_parse_text", "nafgpu_parse_copy_to_host", "nafgpu_parse_hash64", "nafgpu_parse_free",
+    "nafgpu_encode_text",
 ]
 
 
@@ -185,6 +197,17 @@ class Library:
             L.nafgpu_encode_free.restype = None
             L.nafgpu_encode_last_times.argtypes = [POINTER(ctypes.c_double)] * 4
             L.nafgpu_encode_last_times.restype = None
+        if hasattr(L, "nafgpu_parse_text"):                  # (absent from older builds loaded for A/B runs)
+            L.nafgpu_parse_opts_default.argtypes = [POINTER(ParseOpts)]
+            L.nafgpu_parse_opts_default.restype = None
+            L.nafgpu_parse_text.argtypes = [c_void_p, c_uint64, POINTER(ParseOpts), c_int, POINTER(c_void_p), POINTER(ParseResult),
+                                            POINTER(Error)]
+            L.nafgpu_parse_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
+            L.nafgpu_parse_hash64.argtypes = [c_void_p, c_void_p, c_uint64, POINTER(c_uint64)]
+            L.nafgpu_parse_free.argtypes = [c_void_p]
+            L.nafgpu_parse_free.restype = None
+            L.nafgpu_encode_text.argtypes = [c_void_p, c_uint64, POINTER(ParseOpts), POINTER(EncoderOpts), c_int, c_int,
+                                             POINTER(c_void_p), POINTER(c_uint64), POINTER(Error)]
 
     # ---- helpers ---------------------------------------------------------------------------
     def zstd_decompress(self, payload: bytes, size: int, device: int = -1) -> bytes:

@@ -229,7 +229,7 @@ int fail_c(nafgpu_error *err, const Failure &f) {
     return f.status;
 }
 
-Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts *opts, int device, std::vector<uint8_t> &o) {
+Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts *opts, int device, uint64_t line_length, std::vector<uint8_t> &o) {
     if (opts->sequence_type > 3) return Failure::make(NAFGPU_E_INVALID_ARG, "invalid encoder options");
     if (!mask_opts_ok(*opts))
         return Failure::make(NAFGPU_E_INVALID_ARG, "mask needs a nucleotide sequence: sequence set, sequence_type dna or rna");
@@ -338,7 +338,7 @@ Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return device_failure("the mask pass failed");
     }
     // ---- the container (Encoder::write, mod.rs:325-384)
-    put_archive_head(o, *opts, n_rec);
+    put_archive_head(o, *opts, n_rec, line_length);
     auto block = [&](const uint8_t *d_data, uint64_t n, uint64_t original) {
         if (!f.ok()) return;
         std::vector<uint8_t> frame;
@@ -363,6 +363,11 @@ Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts
 }
 
 }  // namespace
+
+Failure encode_device_archive(const nafgpu_encode_source *src, const nafgpu_encoder_opts *opts, int device, uint64_t line_length,
+                              std::vector<uint8_t> &archive) {
+    return encode_device(src, opts, device, line_length, archive);
+}
 
 }  // namespace enc
 }  // namespace nafgpu
@@ -389,7 +394,7 @@ int nafgpu_encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_o
     *bytes = nullptr;
     *n = 0;
     std::vector<uint8_t> archive;
-    Failure f = encode_device(src, opts, device, archive);
+    Failure f = encode_device(src, opts, device, kDefaultLineLength, archive);
     if (!f.ok()) return fail_c(err, f);
     uint8_t *p = static_cast<uint8_t *>(std::malloc(archive.size() ? archive.size() : 1));
     if (!p) return fail_c(err, Failure::make(NAFGPU_E_IO, "out of memory"));

@@ -54,7 +54,8 @@ void put_varint(std::vector<uint8_t> &out, uint64_t v);
 // header, flags, line length, record count: what stands in front of the sections (encoder/mod.rs:327-347)
 // opt.mask needs a nucleotide sequence (sequence set, DNA or RNA)
 bool mask_opts_ok(const nafgpu_encoder_opts &opt);
-void put_archive_head(std::vector<uint8_t> &out, const nafgpu_encoder_opts &opt, uint64_t n_records);
+constexpr uint64_t kDefaultLineLength = 60;      // Header::default().line_length (data.rs:246)
+void put_archive_head(std::vector<uint8_t> &out, const nafgpu_encoder_opts &opt, uint64_t n_records, uint64_t line_length = kDefaultLineLength);
 
 // ---- the device path (encode.cpp) --------------------------------------------------------------
 struct EncTimes {            // milliseconds, summed over the slabs and sections of one call
@@ -66,6 +67,9 @@ struct EncTimes {            // milliseconds, summed over the slabs and sections
 // `src` (host memory, or device memory when src_on_device) -> the frame compress_section(data, ., false) gives, appended to `out`
 Failure compress_section_device(const uint8_t *src, size_t n, bool src_on_device, int device, unsigned n_threads,
                                 std::vector<uint8_t> &out, EncTimes *times);
+// nafgpu_encode_device with the header's line length given (nafgpu_encode_text: the text's own)
+Failure encode_device_archive(const nafgpu_encode_source *src, const nafgpu_encoder_opts *opts, int device, uint64_t line_length,
+                              std::vector<uint8_t> &archive);
 
 // ---- kernels (encode.hip); all pointers are device pointers, every launch is asynchronous ---------
 struct EncStream {           // one Huffman stream of one block

@@ -1068,7 +1068,7 @@ int nucleotide_code(uint8_t c, uint8_t sequence_type) {
 
 bool mask_opts_ok(const nafgpu_encoder_opts &opt) { return !opt.mask || (opt.sequence && opt.sequence_type <= 1); }
 
-void put_archive_head(std::vector<uint8_t> &o, const nafgpu_encoder_opts &opt, uint64_t n_records) {
+void put_archive_head(std::vector<uint8_t> &o, const nafgpu_encoder_opts &opt, uint64_t n_records, uint64_t line_length) {
     o.insert(o.end(), {0x01, 0xF9, 0xEC});                                           // mod.rs:327
     uint8_t flags = 0;                                                               // mod.rs:176-193
     if (opt.id) flags |= 0x20;
@@ -1081,7 +1081,7 @@ void put_archive_head(std::vector<uint8_t> &o, const nafgpu_encoder_opts &opt, u
     } else {
         o.insert(o.end(), {0x02, opt.sequence_type, flags, ' '});
     }
-    put_varint(o, 60);                                                               // Header::default().line_length (data.rs:246)
+    put_varint(o, line_length);                                                      // Header::default().line_length (data.rs:246) unless given
     put_varint(o, n_records);
 }
 

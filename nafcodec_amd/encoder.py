@@ -2,7 +2,8 @@
 (nafcodec-py/nafcodec/lib.pyi:69-87, lib.rs:463-600; the Rust side: encoder/mod.rs:46-384).  Host code, like the
 reference's; every section is written as Huffman-literal Zstandard blocks (include/nafgpu.h: Encoder).  With `device=` the
 sections of compression levels 1 and 2 are compressed by the HIP kernels instead (same bytes), and `encode_device` writes
-an archive from records that are already in HBM.  `mask=True` (no counterpart in the reference, whose mask writer is
+an archive from records that are already in HBM.  `parse_text` makes such records from FASTA / FASTQ text on the device, and
+`encode_text` is both in one call: file in, archive out.  `mask=True` (no counterpart in the reference, whose mask writer is
 commented out) accepts lower-case nucleotides and writes their runs as a Mask section."""
 import ctypes
 import os
@@ -152,9 +153,128 @@ def encode_device(result, *, sequence_type="dna", id=False, comment=False, seque
         lib.c.nafgpu_encode_free(p)
 
 
+_FORMATS = {None: 0, "auto": 0, "fasta": 1, "fastq": 2}
+
+
+def _text_argument(data, n, lib):
+    """-> (pointer argument, length, on device, what to keep alive)"""
+    if isinstance(data, int):                                # a device address, e.g. TextResult.d_text or a tensor's data_ptr()
+        if n is None:
+            raise TypeError("a device pointer needs its length: parse_text(ptr, n)")
+        return c_void_p(data), int(n), 1, None
+    data = bytes(data) if not isinstance(data, bytes) else data
+    n = len(data) if n is None else int(n)
+    if n > len(data):
+        raise ValueError("n is larger than the text")
+    return ctypes.cast(ctypes.c_char_p(data), c_void_p), n, 0, data
+
+
+def _raise_text_error(rc, err):
+    if rc in (_ffi.E_MISSING_FIELD, _ffi.E_INVALID_LENGTH, _ffi.E_INVALID_SEQUENCE, _ffi.E_INVALID_ARG):
+        raise ValueError(err.message.decode("utf-8", "replace"))
+    raise _ffi.NafError.from_c(err)
+
+
+class ParsedText:
+    """What parse_text() returns: the records of a FASTA / FASTQ text in HBM, with the fields encode_device() reads
+    (d_sequence / n_bases, d_quality / n_quality, d_record_end / n_records, d_ids / n_ids_bytes, d_comments /
+    n_comments_bytes), and line_length (the longest sequence line), fastq, n_text, ms (the parse kernels).  The device
+    buffers live until close()."""
+
+    def __init__(self, lib, handle, res):
+        self._lib, self._h = lib, handle
+        for name, _ in _ffi.EncodeSource._fields_:
+            setattr(self, name, getattr(res.src, name))
+        self.d_quality = self.d_quality or None
+        self.line_length, self.n_text, self.fastq, self.ms = res.line_length, res.n_text, bool(res.fastq), res.ms
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError("operation on closed parse result.")
+        return self._h
+
+    def copy_to_host(self, d_ptr, n):
+        buf = ctypes.create_string_buffer(max(int(n), 1))
+        if self._lib.c.nafgpu_parse_copy_to_host(self._handle(), d_ptr, int(n), buf) != _ffi.OK:
+            raise _ffi.NafError(_ffi.E_DEVICE, message="device-to-host copy failed")
+        return buf.raw[:int(n)]
+
+    def hash_device(self, d_ptr, n):
+        out = c_uint64()
+        if self._lib.c.nafgpu_parse_hash64(self._handle(), d_ptr, int(n), byref(out)) != _ffi.OK:
+            raise _ffi.NafError(_ffi.E_DEVICE, message="hashing a device buffer failed")
+        return out.value
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            self._lib.c.nafgpu_parse_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc_value, traceback):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def parse_text(data, n=None, *, format=None, device=None, _lib=None):
+    """FASTA / FASTQ text -> records in HBM, parsed by the HIP kernels (include/nafgpu.h: nafgpu_parse_text has the rules).
+    `data`: bytes-like, or a device address (an int) with its length `n`, which is read where it lies.  `format`: None /
+    "auto" (by the first byte), "fasta" or "fastq".  ValueError for a text the rules refuse."""
+    if format not in _FORMATS:
+        raise ValueError("expected None, 'auto', 'fasta' or 'fastq', got %r" % (format,))
+    lib = _lib or _ffi.default()
+    ptr, n, on_device, keep = _text_argument(data, n, lib)
+    opts = _ffi.ParseOpts(format=_FORMATS[format], text_on_device=on_device)
+    h, res, err = c_void_p(), _ffi.ParseResult(), _ffi.Error()
+    rc = lib.c.nafgpu_parse_text(ptr, n, byref(opts), -1 if device is None else int(device), byref(h), byref(res), byref(err))
+    del keep
+    if rc != _ffi.OK:
+        _raise_text_error(rc, err)
+    return ParsedText(lib, h, res)
+
+
+def encode_text(data, *, sequence_type="dna", id=True, comment=True, sequence=True, quality=None, mask=False, compression_level=1,
+                keep_line_length=True, format=None, device=None, threads=0, _lib=None):
+    """FASTA / FASTQ text (bytes-like) -> an archive (bytes): parse_text and encode_device in one call, what `ennaf` does.
+    `quality=None`: written if the text is FASTQ.  `keep_line_length=False`: the header says 60, and the archive is byte
+    for byte what Encoder writes for the same records."""
+    if sequence_type not in SEQUENCE_TYPES:
+        raise ValueError("expected 'dna', 'rna', 'protein' or 'text', got %r" % (sequence_type,))
+    if format not in _FORMATS:
+        raise ValueError("expected None, 'auto', 'fasta' or 'fastq', got %r" % (format,))
+    _check_mask(mask, sequence_type, sequence)
+    lib = _lib or _ffi.default()
+    ptr, n, on_device, keep = _text_argument(data, None, lib)
+    if quality is None:
+        quality = bytes(data[:1]) == b"@" if format in (None, "auto") else format == "fastq"
+    popts = _ffi.ParseOpts(format=_FORMATS[format], text_on_device=on_device)
+    opts = _ffi.EncoderOpts()
+    lib.c.nafgpu_encoder_opts_default(SEQUENCE_TYPES.index(sequence_type), byref(opts))
+    opts.id, opts.comment, opts.sequence, opts.quality = map(int, (id, comment, sequence, quality))
+    opts.compression_level, opts.threads, opts.mask = int(compression_level), int(threads), int(bool(mask))
+    p, n_out, err = c_void_p(), c_uint64(), _ffi.Error()
+    rc = lib.c.nafgpu_encode_text(ptr, n, byref(popts), byref(opts), int(bool(keep_line_length)), -1 if device is None else int(device),
+                                  byref(p), byref(n_out), byref(err))
+    del keep
+    if rc != _ffi.OK:
+        _raise_text_error(rc, err)
+    try:
+        return ctypes.string_at(p, n_out.value)
+    finally:
+        lib.c.nafgpu_encode_free(p)
+
+
 def open_binary(path):
     import builtins
     return builtins.open(os.fspath(path), "wb")
 
 
-__all__ = ["Encoder", "Record", "encode_device", "zstd_compress"]
+__all__ = ["Encoder", "ParsedText", "Record", "encode_device", "encode_text", "parse_text", "zstd_compress"]
