@@ -253,6 +253,9 @@ public:
     EncoderBuilder &mask(bool v) { o_.mask = v; return *this; }
     // (no counterpart in the reference) compress the sections on that GPU (-1: the current one); compression_level 1 or 2
     EncoderBuilder &device(int v) { device_ = v; return *this; }
+    // (no counterpart in the reference) with device(), encode_device() or encode_text(): compression_level 0 and >= 3 too,
+    // the LZ matches found on the GPU (nafgpu_encoder_opts.device_lz); the host encoder ignores it
+    EncoderBuilder &device_lz(bool v) { o_.device_lz = v; return *this; }
     Encoder with_memory() const {                                                    // mod.rs:161-163
         nafgpu_encoder *e = nullptr;
         nafgpu_error err{};
@@ -262,7 +265,7 @@ public:
             err.status = nafgpu_encoder_set_device(e, device_);
             if (err.status != NAFGPU_OK) {
                 std::snprintf(err.message, sizeof err.message, "%s",
-                              err.status == NAFGPU_E_DEVICE ? "no usable HIP device" : "device encoding needs compression_level 1 or 2");
+                              err.status == NAFGPU_E_DEVICE ? "no usable HIP device" : "device encoding needs compression_level 1 or 2, or device_lz(true)");
                 throw Error(err);
             }
         }
@@ -277,7 +280,7 @@ private:
 
 // (no counterpart in the reference) records that are in HBM -> an archive, the bytes Encoder::write gives when the same
 // records are pushed one by one: nafgpu_encode_device.  `fields` says what is written (id / comment / sequence / quality,
-// mask, compression_level 1 or 2); the source's pointers must agree with it.
+// mask, compression_level 1 or 2, or any level with device_lz(true)); the source's pointers must agree with it.
 inline std::string encode_device(const nafgpu_encode_source &src, const EncoderBuilder &fields, int device = -1) {
     uint8_t *p = nullptr;
     uint64_t n = 0;

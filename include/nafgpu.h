@@ -333,7 +333,9 @@ typedef struct {
     uint8_t sequence_type;       /* 0 dna, 1 rna, 2 protein, 3 text (EncoderBuilder::new, mod.rs:81-90) */
     uint8_t id, comment, sequence, quality;   /* opt-in fields (mod.rs:112-145); all 0 by default */
     uint8_t mask;                /* write a Mask section from the case of the letters (see above); 0 by default */
-    uint8_t reserved[2];
+    uint8_t device_lz;           /* the device calls below accept compression_level 0 and >= 3 and find the LZ matches on the GPU
+                                    (see "encoding on the device"); 0 by default; the host encoder ignores it */
+    uint8_t reserved[1];
     int32_t compression_level;   /* mod.rs:147-157; 0 or >= 3: with LZ matches, 1-2: literals only (see above) */
     uint32_t threads;            /* blocks are encoded in parallel when the archive is written; 0 = hardware concurrency */
 } nafgpu_encoder_opts;
@@ -355,17 +357,23 @@ void nafgpu_encoder_free(nafgpu_encoder *enc);
 
 /* ---- encoding on the device: literal-only sections (compression_level 1 and 2) --------------
  * The kernels count symbols and write the bit streams; the host decides every block from the counts with the same
- * function the host encoder uses, so the bytes are those of the host path.  Blocks with LZ sequences stay host-only. */
+ * function the host encoder uses, so the bytes are those of the host path.  Blocks with LZ sequences (levels 0 and >= 3)
+ * are host-only unless opts.device_lz is set: then the three device calls below take those levels too, the matches are
+ * found by kernels (inside each 128 KiB block), and the archive is a valid and deterministic one of its own -- the same
+ * container, not the host encoder's bytes.  At levels 1 and 2 the flag changes nothing. */
 
 /* L0 counterpart of nafgpu_zstd_decompress: `src` -> one magicless frame of literal-only blocks, the bytes the host
  * Encoder writes for this section at compression_level 1.  Host in, host out, the work on the GPU.  Any size: inputs
  * larger than a slab (a multiple of 64 blocks = 8 MiB, so that slabs end on chunk boundaries and stay independent)
  * go slab by slab.  *produced > cap: NAFGPU_E_INVALID_ARG with *produced set to the size needed. */
 int nafgpu_zstd_compress(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *produced, int device, nafgpu_error *err);
+/* The same call with blocks that carry LZ sequences where that is smaller (what opts.device_lz writes for a section): one
+ * magicless frame `00 50`, predefined sequence tables, every offset a new offset, no match in front of its block. */
+int nafgpu_zstd_compress_lz(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *produced, int device, nafgpu_error *err);
 
 /* Encoder::write on the GPU for sections already pushed: call before nafgpu_encoder_finish.  device >= 0 or -1 (current):
  * finish compresses every section with the kernels; never called: host code as before.  NAFGPU_E_INVALID_ARG when the
- * encoder's compression_level is not 1 or 2 (blocks with LZ sequences are host-only), NAFGPU_E_DEVICE when there is no GPU. */
+ * encoder's compression_level is not 1 or 2 and opts.device_lz is 0, NAFGPU_E_DEVICE when there is no GPU. */
 int nafgpu_encoder_set_device(nafgpu_encoder *enc, int device);
 
 /* The way back from nafgpu_decode_all_device: records that are in HBM -> an archive, without a host push per record. */
@@ -377,7 +385,8 @@ typedef struct {
     const uint8_t *d_comments;  uint64_t n_comments_bytes;
 } nafgpu_encode_source;   /* a NULL pointer = that field is not written; opts->id/comment/sequence/quality must agree */
 /* The archive nafgpu_encoder_finish gives when the same records are pushed one by one, byte for byte (compression_level 1
- * or 2, else NAFGPU_E_INVALID_ARG).  The host encoder's checks in bulk: quality total != sequence total, or a last record
+ * or 2, else NAFGPU_E_INVALID_ARG; with opts->device_lz any level, and at 0 and >= 3 the archive
+ * nafgpu_encoder_set_device + finish give).  The host encoder's checks in bulk: quality total != sequence total, or a last record
  * end that is not the total: NAFGPU_E_INVALID_LENGTH; ids / comments that are not n_records NUL-terminated strings:
  * NAFGPU_E_MISSING_FIELD; a letter the nucleotide table refuses (lower case included unless opts->mask is set; with it, a
  * lower-case letter whose upper-case form is refused): NAFGPU_E_INVALID_SEQUENCE, the message names the first one.  With
@@ -386,8 +395,9 @@ typedef struct {
 int nafgpu_encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts *opts, int device,
                          uint8_t **bytes, uint64_t *n, nafgpu_error *err);
 void nafgpu_encode_free(uint8_t *bytes);
-/* what the calling thread's last nafgpu_zstd_compress / nafgpu_encode_device took, in milliseconds: k_enc_hist and
- * k_enc_streams + k_enc_scatter (HIP events, summed over slabs and sections), the host plan between them, the whole call
+/* what the calling thread's last nafgpu_zstd_compress / nafgpu_encode_device took, in milliseconds: k_enc_hist (device_lz:
+ * and the match, parse and literal-count kernels) and k_enc_streams + k_enc_scatter (device_lz: and the sequence bits)
+ * (HIP events, summed over slabs and sections), the host plan between them, the whole call
  * (tools/encode_probe.py) */
 void nafgpu_encode_last_times(double *hist_ms, double *streams_ms, double *plan_ms, double *total_ms);
 
@@ -432,7 +442,7 @@ int nafgpu_parse_hash64(nafgpu_parsed *parsed, const void *d_ptr, uint64_t n, ui
 void nafgpu_parse_free(nafgpu_parsed *parsed);
 /* Parse and encode in one call.  With keep_line_length = 0 the archive is, byte for byte, what the host Encoder
  * writes when the same records are pushed one by one; with 1 the header carries the text's line_length instead of 60 and
- * nothing else differs.  compression_level 1 or 2; opts->quality with FASTA text: NAFGPU_E_MISSING_FIELD; opts->mask as
+ * nothing else differs.  compression_level 1 or 2 (any with opts->device_lz); opts->quality with FASTA text: NAFGPU_E_MISSING_FIELD; opts->mask as
  * for the encoders.  Fields of the text that opts does not name are dropped.  *bytes: free with nafgpu_encode_free. */
 int nafgpu_encode_text(const uint8_t *text, uint64_t n, const nafgpu_parse_opts *popts, const nafgpu_encoder_opts *opts,
                        int keep_line_length, int device, uint8_t **bytes, uint64_t *n_out, nafgpu_error *err);

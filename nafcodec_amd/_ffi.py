@@ -84,7 +84,8 @@ class SynthArchive(Structure):
 
 class EncoderOpts(Structure):
     _fields_ = [("sequence_type", c_uint8), ("id", c_uint8), ("comment", c_uint8), ("sequence", c_uint8), ("quality", c_uint8),
-                ("mask", c_uint8), ("reserved", c_uint8 * 2), ("compression_level", ctypes.c_int32), ("threads", c_uint32)]
+                ("mask", c_uint8), ("device_lz", c_uint8), ("reserved", c_uint8 * 1), ("compression_level", ctypes.c_int32),
+                ("threads", c_uint32)]
 
 
 class EncodeSource(Structure):
@@ -121,7 +122,7 @@ EXPORTS = [
     "nafgpu_shard_import_halo", "nafgpu_shard_finish", "nafgpu_next_batch", "nafgpu_trim_device_memory",
     "nafgpu_zstd_compress", "nafgpu_encoder_set_device", "nafgpu_encode_device", "nafgpu_encode_free", "nafgpu_encode_last_times",
     "nafgpu_parse_opts_default", "nafgpu_parse_text", "nafgpu_parse_copy_to_host", "nafgpu_parse_hash64", "nafgpu_parse_free",
-    "nafgpu_encode_text",
+    "nafgpu_encode_text", "nafgpu_zstd_compress_lz",
 ]
 
 
@@ -197,6 +198,8 @@ class Library:
             L.nafgpu_encode_free.restype = None
             L.nafgpu_encode_last_times.argtypes = [POINTER(ctypes.c_double)] * 4
             L.nafgpu_encode_last_times.restype = None
+        if hasattr(L, "nafgpu_zstd_compress_lz"):            # (absent from older builds loaded for A/B runs)
+            L.nafgpu_zstd_compress_lz.argtypes = L.nafgpu_zstd_compress.argtypes
         if hasattr(L, "nafgpu_parse_text"):                  # (absent from older builds loaded for A/B runs)
             L.nafgpu_parse_opts_default.argtypes = [POINTER(ParseOpts)]
             L.nafgpu_parse_opts_default.restype = None
@@ -219,12 +222,14 @@ class Library:
             raise NafError.from_c(err)
         return buf.raw[:produced.value]
 
-    def zstd_compress(self, data: bytes, device: int = -1) -> bytes:
-        """One section -> one magicless frame of literal-only blocks, written on the GPU (nafgpu_zstd_compress)."""
+    def zstd_compress(self, data: bytes, device: int = -1, lz: bool = False) -> bytes:
+        """One section -> one magicless frame written on the GPU: literal-only blocks (nafgpu_zstd_compress), or with `lz`
+        blocks with LZ sequences (nafgpu_zstd_compress_lz)."""
         cap = len(data) + 3 * (len(data) // (128 << 10) + 1) + 2      # nothing but raw blocks: the largest frame there is
         buf = ctypes.create_string_buffer(cap)
         produced, err = c_size_t(0), Error()
-        rc = self.c.nafgpu_zstd_compress(data, len(data), buf, cap, byref(produced), device, byref(err))
+        fn = self.c.nafgpu_zstd_compress_lz if lz else self.c.nafgpu_zstd_compress
+        rc = fn(data, len(data), buf, cap, byref(produced), device, byref(err))
         if rc != OK:
             raise NafError.from_c(err)
         return buf.raw[:produced.value]

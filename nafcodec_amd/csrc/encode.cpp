@@ -6,6 +6,12 @@
 //   chunk in order: a block may reuse the table of the one before) -> offsets, stream records, tables and header bytes to
 //   the device -> k_enc_streams + k_enc_scatter -> the slab's piece of the frame back to the host.
 // The frame is the one compress_section(data, ., lz = false) writes: plan_block is the same function on both paths.
+//
+// With LZ (opts.device_lz at compression levels 0 and >= 3) four kernels run in front of the host's decisions:
+//   k_enc_lz_match -> k_enc_lz_parse -> k_enc_lz_hist + k_enc_lz_seqbits -> counts of the block and of its literals, the
+//   number of sequences and the size of their bitstream to the host -> per block the smaller of plan_block's block and
+//   [plan_literals + sequences] -> k_enc_streams over the input and over the literal buffers, k_enc_scatter.
+// The container is that of compress_section(data, ., lz = true); the matches are the device matcher's own.
 #include "encode.h"
 
 #include <algorithm>
@@ -40,6 +46,13 @@ struct SlabPlan {
     std::vector<uint8_t> blob;
     uint64_t out_bytes = 0;
     uint32_t max_stream = 0;
+    std::vector<EncStream> lit_streams;      // LZ: streams whose symbols lie in the literal buffers
+};
+
+struct LzBlockPlan {         // a block with sequences: the literals plan and what stands between the literals and the bitstream
+    bool taken = false;
+    BlockPlan lits;
+    uint32_t n_seq = 0, seq_bytes = 0;
 };
 
 // Sections of one call share a stream, the events and the buffers.
@@ -68,8 +81,10 @@ public:
     EncTimes times;
 
     // `src` -> the section's frame, appended to `out`
-    Failure compress(const uint8_t *src, size_t n, bool src_on_device, unsigned n_threads, std::vector<uint8_t> &out) {
-        size_t slab = size_t(512) << 20;
+    // lz: blocks with sequences (a section under 64 bytes is raw blocks either way, as compress_section writes it)
+    Failure compress(const uint8_t *src, size_t n, bool src_on_device, unsigned n_threads, bool lz, std::vector<uint8_t> &out) {
+        lz = lz && n >= 64;
+        size_t slab = size_t(lz ? 128 : 512) << 20;                   // LZ: 14 bytes of scratch per input byte
         if (const char *e = hook_env("NAFGPU_ENC_SLAB_MIB")) {        // tests: several slabs over a small section
             const size_t mib = std::max<size_t>(1, std::strtoull(e, nullptr, 10));
             slab = ((mib + 7) / 8 * 8) << 20;                          // whole chunks of 64 blocks
@@ -78,7 +93,7 @@ public:
         size_t off = 0;
         do {
             const size_t sn = std::min(slab, n - off);
-            Failure f = compress_slab(src + off, sn, src_on_device, off == 0, off + sn == n, n_threads, out);
+            Failure f = compress_slab(src + off, sn, src_on_device, off == 0, off + sn == n, n_threads, lz, out);
             if (!f.ok()) return f;
             off += sn;
         } while (off < n);
@@ -86,7 +101,7 @@ public:
     }
 
 private:
-    Failure compress_slab(const uint8_t *src, size_t sn, bool src_on_device, bool first, bool last, unsigned n_threads,
+    Failure compress_slab(const uint8_t *src, size_t sn, bool src_on_device, bool first, bool last, unsigned n_threads, bool lz,
                           std::vector<uint8_t> &out) {
         const uint32_t nb = static_cast<uint32_t>(std::max<size_t>(1, (sn + kBlockMax - 1) / kBlockMax));
         const uint8_t *d_in = src;
@@ -97,29 +112,65 @@ private:
         }
         const uint32_t status0[4] = {0, 0, 0, 0};
         if (!d_status_.alloc(sizeof status0) || !d_hist_.alloc(size_t(nb) * 4096)) return device_failure("out of device memory");
+        if (lz) {
+            const size_t padded = size_t(nb) * kBlockMax;
+            if (!d_match_.alloc_items(padded, 4) || !d_exits_.alloc_items(padded, 4) || !d_lits_.alloc(padded) || !d_bits_.alloc(padded) ||
+                !d_seqs_.alloc_items(size_t(nb) * kLzMaxSeq, sizeof(LzSeq)) || !d_info_.alloc_items(nb, sizeof(LzBlockInfo)) ||
+                !d_lit_hist_.alloc(size_t(nb) * 4096))
+                return device_failure("out of device memory");
+            if (!d_seq_tables_.size()) {
+                LzSeqTables t;
+                lz_seq_tables(&t);
+                if (!d_seq_tables_.upload(&t, sizeof t, stream_) || hipStreamSynchronize(stream_) != hipSuccess)
+                    return device_failure("out of device memory");
+            }
+            lit_hist_.resize(size_t(nb) * 1024);
+            info_.resize(nb);
+        }
         hist_.resize(size_t(nb) * 1024);
         bool ok = hipMemcpyAsync(d_status_.bytes(), status0, sizeof status0, hipMemcpyHostToDevice, stream_) == hipSuccess;
         ok = ok && hipEventRecord(ev_[0], stream_) == hipSuccess;
         if (sn >= 64) launch_enc_hist(stream_, d_in, sn, nb, d_hist_.as<uint32_t>());
+        if (lz) {
+            launch_enc_lz_match(stream_, d_in, sn, nb, d_match_.as<uint32_t>());
+            launch_enc_lz_parse(stream_, d_in, sn, nb, d_match_.as<uint32_t>(), d_exits_.as<uint32_t>(), d_info_.as<LzBlockInfo>(),
+                                d_seqs_.as<LzSeq>(), d_lits_.bytes());
+            launch_enc_lz_hist(stream_, d_lits_.bytes(), d_info_.as<LzBlockInfo>(), nb, d_lit_hist_.as<uint32_t>());
+        }
         ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(ev_[1], stream_) == hipSuccess;
+        if (lz) {
+            ok = ok && hipEventRecord(ev_[4], stream_) == hipSuccess;
+            launch_enc_lz_seqbits(stream_, d_seqs_.as<LzSeq>(), d_seq_tables_.as<LzSeqTables>(), nb, d_info_.as<LzBlockInfo>(), d_bits_.bytes());
+            ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(ev_[5], stream_) == hipSuccess;
+            ok = ok && hipMemcpyAsync(lit_hist_.data(), d_lit_hist_.bytes(), size_t(nb) * 4096, hipMemcpyDeviceToHost, stream_) == hipSuccess;
+            ok = ok && hipMemcpyAsync(info_.data(), d_info_.bytes(), size_t(nb) * sizeof(LzBlockInfo), hipMemcpyDeviceToHost, stream_) == hipSuccess;
+        }
         if (sn >= 64) ok = ok && hipMemcpyAsync(hist_.data(), d_hist_.bytes(), size_t(nb) * 4096, hipMemcpyDeviceToHost, stream_) == hipSuccess;
         ok = ok && hipStreamSynchronize(stream_) == hipSuccess;
         if (!ok) return device_failure("the histogram pass failed");
 
         const double t0 = now_ms();
         SlabPlan sp;
-        plan_slab(sn, nb, first, last, n_threads, &sp);
+        plan_slab(sn, nb, first, last, n_threads, lz, &sp);
         times.plan += now_ms() - t0;
 
         if (!d_out_.alloc(sp.out_bytes) || !d_streams_.upload(sp.streams.data(), sp.streams.size() * sizeof(EncStream), stream_) ||
             !d_tables_.upload(sp.tables.data(), sp.tables.size() * sizeof(EncTable), stream_) ||
             !d_copies_.upload(sp.copies.data(), sp.copies.size() * sizeof(EncCopy), stream_) ||
-            !d_blob_.upload(sp.blob.data(), sp.blob.size(), stream_))
+            !d_blob_.upload(sp.blob.data(), sp.blob.size(), stream_) ||
+            (lz && !d_lit_streams_.upload(sp.lit_streams.data(), sp.lit_streams.size() * sizeof(EncStream), stream_)))
             return device_failure("out of device memory");
         ok = hipEventRecord(ev_[2], stream_) == hipSuccess;
         launch_enc_streams(stream_, d_in, d_streams_.as<EncStream>(), static_cast<uint32_t>(sp.streams.size()), d_tables_.as<EncTable>(),
                            sp.max_stream, d_out_.bytes(), d_status_.as<uint32_t>());
-        launch_enc_scatter(stream_, d_in, d_blob_.bytes(), d_copies_.as<EncCopy>(), static_cast<uint32_t>(sp.copies.size()), d_out_.bytes());
+        if (lz) {
+            launch_enc_streams(stream_, d_lits_.bytes(), d_lit_streams_.as<EncStream>(), static_cast<uint32_t>(sp.lit_streams.size()),
+                               d_tables_.as<EncTable>(), sp.max_stream, d_out_.bytes(), d_status_.as<uint32_t>());
+            launch_enc_scatter_lz(stream_, d_in, d_blob_.bytes(), d_lits_.bytes(), d_bits_.bytes(), d_copies_.as<EncCopy>(),
+                                  static_cast<uint32_t>(sp.copies.size()), d_out_.bytes());
+        } else {
+            launch_enc_scatter(stream_, d_in, d_blob_.bytes(), d_copies_.as<EncCopy>(), static_cast<uint32_t>(sp.copies.size()), d_out_.bytes());
+        }
         ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(ev_[3], stream_) == hipSuccess;
         uint32_t status[4] = {0, 0, 0, 0};
         const size_t at = out.size();
@@ -138,11 +189,13 @@ private:
         float a = 0, b = 0;
         if (hipEventElapsedTime(&a, ev_[0], ev_[1]) == hipSuccess && hipEventElapsedTime(&b, ev_[2], ev_[3]) == hipSuccess)
             times.hist += a, times.streams += b;
+        if (lz && hipEventElapsedTime(&a, ev_[4], ev_[5]) == hipSuccess) times.streams += a;
         return Failure();
     }
 
-    void plan_slab(size_t sn, uint32_t nb, bool first, bool last, unsigned n_threads, SlabPlan *sp) {
+    void plan_slab(size_t sn, uint32_t nb, bool first, bool last, unsigned n_threads, bool lz, SlabPlan *sp) {
         std::vector<BlockPlan> plans(nb);
+        std::vector<LzBlockPlan> lz_plans(lz ? nb : 0);
         const uint32_t n_chunks = static_cast<uint32_t>((nb + kChunkBlocks - 1) / kChunkBlocks);
         std::atomic<uint32_t> next{0};
         auto worker = [&]() {
@@ -152,8 +205,26 @@ private:
                 HufCode prev{};
                 for (uint32_t b = c * kChunkBlocks; b < std::min<uint64_t>(nb, (c + 1) * kChunkBlocks); b++) {
                     const size_t p0 = size_t(b) * kBlockMax, bn = std::min<size_t>(kBlockMax, sn - p0);
-                    plan_block(reinterpret_cast<const uint32_t(*)[256]>(hist_.data() + size_t(b) * 1024), bn, last && b == nb - 1, &prev,
-                               &plans[b]);
+                    const auto counts = reinterpret_cast<const uint32_t(*)[256]>(hist_.data() + size_t(b) * 1024);
+                    if (!lz || !info_[b].n_seq || info_[b].seq_bytes == kLzSeqOverflow) {
+                        plan_block(counts, bn, last && b == nb - 1, &prev, &plans[b]);
+                        continue;
+                    }
+                    // with sequences: literals, sequence count, Symbol_Compression_Modes, bitstream -- if that is the smaller block
+                    LzBlockPlan &lp = lz_plans[b];
+                    lp.n_seq = info_[b].n_seq;
+                    lp.seq_bytes = info_[b].seq_bytes;
+                    plan_literals(reinterpret_cast<const uint32_t(*)[256]>(lit_hist_.data() + size_t(b) * 1024), info_[b].n_lit, &prev, &lp.lits);
+                    const size_t body = lp.lits.total + (lp.n_seq < 128 ? 1 : 2) + 1 + lp.seq_bytes;
+                    HufCode prev_plain = prev;
+                    plan_block(counts, bn, last && b == nb - 1, &prev_plain, &plans[b]);
+                    if (body < plans[b].total - 3) {
+                        lp.taken = true;
+                        plans[b].total = 3 + body;
+                        if (lp.lits.mode == kHufNew) prev = lp.lits.code;
+                    } else {
+                        prev = prev_plain;
+                    }
                 }
             }
         };
@@ -169,30 +240,61 @@ private:
             sp->blob.insert(sp->blob.end(), p, p + len);
             pos += len;
         };
-        const uint8_t frame_head[2] = {0x00, 0x48};            // FHD: no content size, no checksum, no dictionary; window 512 KiB
+        // FHD: no content size, no checksum, no dictionary; window 512 KiB, or 1 MiB as compress_section(., lz = true) says it
+        const uint8_t frame_head[2] = {0x00, static_cast<uint8_t>(lz ? 0x50 : 0x48)};
         if (first) from_blob(frame_head, 2);
         sp->blob.push_back(0x00);                               // Number_of_Sequences = 0, behind every compressed block
         const uint64_t zero_at = sp->blob.size() - 1;
+        auto add_streams = [&](std::vector<EncStream> &list, const BlockPlan &p, uint64_t p0) {
+            if (p.mode == kHufNew) {
+                EncTable t;
+                std::memcpy(t.code, p.code.code, sizeof t.code);
+                std::memcpy(t.len, p.code.len, sizeof t.len);
+                sp->tables.push_back(t);
+            }
+            const size_t q = (p.n + 3) / 4;
+            for (int k = 0; k < 4; k++) {
+                const uint32_t n_sym = static_cast<uint32_t>(k < 3 ? q : p.n - 3 * q);
+                list.push_back(EncStream{p0 + k * q, pos, n_sym, p.stream_size[k], static_cast<uint32_t>(sp->tables.size() - 1), 0});
+                sp->max_stream = std::max(sp->max_stream, p.stream_size[k]);
+                pos += p.stream_size[k];
+            }
+        };
         for (uint32_t b = 0; b < nb; b++) {
             const BlockPlan &p = plans[b];
             const uint64_t p0 = uint64_t(b) * kBlockMax, end = pos + p.total;
+            if (lz && lz_plans[b].taken) {
+                const LzBlockPlan &lp = lz_plans[b];
+                const uint32_t bh = static_cast<uint32_t>((p.total - 3) << 3) | (2u << 1) | (last && b == nb - 1 ? 1u : 0u);
+                const uint8_t bh3[3] = {static_cast<uint8_t>(bh), static_cast<uint8_t>(bh >> 8), static_cast<uint8_t>(bh >> 16)};
+                from_blob(bh3, 3);
+                from_blob(lp.lits.head.data(), lp.lits.head.size());
+                if (lp.lits.mode == kRaw && lp.lits.n) {
+                    sp->copies.push_back(EncCopy{p0, pos, static_cast<uint32_t>(lp.lits.n), kCopyLiterals});
+                    pos += lp.lits.n;
+                } else if (lp.lits.mode == kHufNew || lp.lits.mode == kHufTreeless) {
+                    add_streams(sp->lit_streams, lp.lits, p0);
+                }
+                // Number_of_Sequences (one byte under 128, else two; a block holds fewer than 0x7F00), then "predefined x 3"
+                uint8_t sh[3];
+                size_t shn = 0;
+                if (lp.n_seq < 128) {
+                    sh[shn++] = static_cast<uint8_t>(lp.n_seq);
+                } else {
+                    sh[shn++] = static_cast<uint8_t>((lp.n_seq >> 8) + 128);
+                    sh[shn++] = static_cast<uint8_t>(lp.n_seq & 0xFF);
+                }
+                sh[shn++] = 0x00;
+                from_blob(sh, shn);
+                sp->copies.push_back(EncCopy{p0, pos, lp.seq_bytes, kCopySeqBits});
+                pos = end;
+                continue;
+            }
             from_blob(p.head.data(), p.head.size());
             if (p.mode == kRaw && p.n) {
                 sp->copies.push_back(EncCopy{p0, pos, static_cast<uint32_t>(p.n), 1});
             } else if (p.mode == kHufNew || p.mode == kHufTreeless) {
-                if (p.mode == kHufNew) {
-                    EncTable t;
-                    std::memcpy(t.code, p.code.code, sizeof t.code);
-                    std::memcpy(t.len, p.code.len, sizeof t.len);
-                    sp->tables.push_back(t);
-                }
-                const size_t q = (p.n + 3) / 4;
-                for (int k = 0; k < 4; k++) {
-                    const uint32_t n_sym = static_cast<uint32_t>(k < 3 ? q : p.n - 3 * q);
-                    sp->streams.push_back(EncStream{p0 + k * q, pos, n_sym, p.stream_size[k], static_cast<uint32_t>(sp->tables.size() - 1), 0});
-                    sp->max_stream = std::max(sp->max_stream, p.stream_size[k]);
-                    pos += p.stream_size[k];
-                }
+                add_streams(sp->streams, p, p0);
                 sp->copies.push_back(EncCopy{zero_at, pos, 1, 0});
             }
             pos = end;
@@ -202,19 +304,21 @@ private:
 
     int device_ = -1;
     hipStream_t stream_ = nullptr;
-    hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<uint32_t> hist_;
+    hipEvent_t ev_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    std::vector<uint32_t> hist_, lit_hist_;
+    std::vector<LzBlockInfo> info_;
     DevBuf d_in_, d_hist_, d_out_, d_streams_, d_tables_, d_copies_, d_blob_, d_status_;
+    DevBuf d_match_, d_exits_, d_lits_, d_bits_, d_seqs_, d_info_, d_lit_hist_, d_lit_streams_, d_seq_tables_;   // LZ
 };
 
 }  // namespace
 
-Failure compress_section_device(const uint8_t *src, size_t n, bool src_on_device, int device, unsigned n_threads,
+Failure compress_section_device(const uint8_t *src, size_t n, bool src_on_device, int device, unsigned n_threads, bool lz,
                                 std::vector<uint8_t> &out, EncTimes *times) {
     const double t0 = now_ms();
     SectionEncoder se;
     Failure f = se.init(device);
-    if (f.ok()) f = se.compress(src, n, src_on_device, n_threads, out);
+    if (f.ok()) f = se.compress(src, n, src_on_device, n_threads, lz, out);
     se.times.total = now_ms() - t0;
     g_last_times = se.times;
     if (times) *times = se.times;
@@ -233,7 +337,8 @@ Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts
     if (opts->sequence_type > 3) return Failure::make(NAFGPU_E_INVALID_ARG, "invalid encoder options");
     if (!mask_opts_ok(*opts))
         return Failure::make(NAFGPU_E_INVALID_ARG, "mask needs a nucleotide sequence: sequence set, sequence_type dna or rna");
-    if (opts->compression_level != 1 && opts->compression_level != 2)
+    const bool lz = opts->compression_level != 1 && opts->compression_level != 2;
+    if (lz && !opts->device_lz)
         return Failure::make(NAFGPU_E_INVALID_ARG, "the device encoder writes literal-only blocks: compression_level 1 or 2");
     if ((opts->id != 0) != (src->d_ids != nullptr) || (opts->comment != 0) != (src->d_comments != nullptr) ||
         (opts->sequence != 0) != (src->d_sequence != nullptr) || (opts->quality != 0) != (src->d_quality != nullptr))
@@ -342,7 +447,7 @@ Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts
     auto block = [&](const uint8_t *d_data, uint64_t n, uint64_t original) {
         if (!f.ok()) return;
         std::vector<uint8_t> frame;
-        f = se.compress(d_data, n, true, opts->threads, frame);
+        f = se.compress(d_data, n, true, opts->threads, lz, frame);
         if (!f.ok()) return;
         put_varint(o, original);
         put_varint(o, frame.size());
@@ -377,15 +482,23 @@ using namespace nafgpu::enc;
 
 extern "C" {
 
-int nafgpu_zstd_compress(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *produced, int device, nafgpu_error *err) {
+static int zstd_compress_c(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *produced, int device, bool lz, nafgpu_error *err) {
     if ((!src && n) || (!dst && cap) || !produced || device < -1) return fail_c(err, Failure::make(NAFGPU_E_INVALID_ARG, "invalid argument"));
     std::vector<uint8_t> frame;
-    Failure f = compress_section_device(src, n, false, device, 0, frame, nullptr);
+    Failure f = compress_section_device(src, n, false, device, 0, lz, frame, nullptr);
     if (!f.ok()) return fail_c(err, f);
     *produced = frame.size();
     if (frame.size() > cap) return fail_c(err, Failure::make(NAFGPU_E_INVALID_ARG, "destination buffer too small"));
     if (!frame.empty()) std::memcpy(dst, frame.data(), frame.size());
     return fail_c(err, Failure());
+}
+
+int nafgpu_zstd_compress(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *produced, int device, nafgpu_error *err) {
+    return zstd_compress_c(src, n, dst, cap, produced, device, false, err);
+}
+
+int nafgpu_zstd_compress_lz(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t *produced, int device, nafgpu_error *err) {
+    return zstd_compress_c(src, n, dst, cap, produced, device, true, err);
 }
 
 int nafgpu_encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts *opts, int device, uint8_t **bytes, uint64_t *n,

@@ -1,5 +1,5 @@
 // encode.h -- what the host encoder (synth.cpp), the device encoder's front end (encode.cpp) and its kernels
-// (encode.hip) share: the block plan of a literal-only section, and the launchers.
+// (encode.hip) share: the block plan of a literal-only section, the literals plan of a block with sequences, and the launchers.
 //
 // A literal-only block is decided by symbol counts alone (plan_block); only writing its four bit streams needs the
 // bytes.  The host path is  count -> plan_block -> emit_block;  the device path is  k_enc_hist -> plan_block on the host
@@ -46,6 +46,10 @@ void count_block(const uint8_t *data, size_t n, uint32_t counts[4][256]);
 // same chunk; replaced only when this block is emitted compressed with a new tree.
 void plan_block(const uint32_t counts[4][256], size_t n, bool last, HufCode *prev, BlockPlan *plan);
 void emit_block(const BlockPlan &plan, const uint8_t *data, std::vector<uint8_t> &out);
+// The Literals_Section of a block with sequences (synth.cpp); `counts` as count_block gives them for the literal bytes.
+// plan->head: literals header (+ RLE byte, or tree and jump table); plan->total: the section's bytes.  *prev is only read.
+void plan_literals(const uint32_t counts[4][256], size_t n, const HufCode *prev, BlockPlan *plan);
+constexpr uint32_t kLzMinMatch = 6;     // shortest match either encoder takes
 
 // one section -> one magicless frame (host code; lz: blocks with LZ sequences, compression levels 0 and >= 3)
 void compress_section(const std::vector<uint8_t> &data, unsigned n_threads, bool lz, std::vector<uint8_t> &out);
@@ -59,13 +63,14 @@ void put_archive_head(std::vector<uint8_t> &out, const nafgpu_encoder_opts &opt,
 
 // ---- the device path (encode.cpp) --------------------------------------------------------------
 struct EncTimes {            // milliseconds, summed over the slabs and sections of one call
-    double hist = 0;         // HIP events around k_enc_hist
-    double streams = 0;      // HIP events around k_enc_streams + k_enc_scatter
+    double hist = 0;         // HIP events around k_enc_hist (device_lz: and k_enc_lz_match, k_enc_lz_parse, k_enc_lz_hist)
+    double streams = 0;      // HIP events around k_enc_streams + k_enc_scatter (device_lz: and k_enc_lz_seqbits)
     double plan = 0;         // host: plan_block over the histograms and building the upload
     double total = 0;        // wall time of the call
 };
-// `src` (host memory, or device memory when src_on_device) -> the frame compress_section(data, ., false) gives, appended to `out`
-Failure compress_section_device(const uint8_t *src, size_t n, bool src_on_device, int device, unsigned n_threads,
+// `src` (host memory, or device memory when src_on_device) -> the frame compress_section(data, ., false) gives, appended to `out`;
+// lz: a frame of blocks with sequences found by the device matcher instead
+Failure compress_section_device(const uint8_t *src, size_t n, bool src_on_device, int device, unsigned n_threads, bool lz,
                                 std::vector<uint8_t> &out, EncTimes *times);
 // nafgpu_encode_device with the header's line length given (nafgpu_encode_text: the text's own)
 Failure encode_device_archive(const nafgpu_encode_source *src, const nafgpu_encoder_opts *opts, int device, uint64_t line_length,
@@ -88,8 +93,9 @@ struct EncCopy {             // k_enc_scatter: `len` bytes to out + dst, from th
     uint64_t src;
     uint64_t dst;
     uint32_t len;
-    uint32_t from_input;
+    uint32_t from_input;     // kCopyBlob, kCopyInput; device_lz: kCopyLiterals, kCopySeqBits
 };
+constexpr uint32_t kCopyBlob = 0, kCopyInput = 1, kCopyLiterals = 2, kCopySeqBits = 3;
 constexpr uint32_t kEncStBadLetter = 1, kEncStStreamSize = 2;    // status[0] bits; status[2..3]: u64, the complement of the first bad letter's index
 
 // mask: a lower-case letter is packed as its upper-case form
@@ -114,6 +120,41 @@ void launch_enc_streams(hipStream_t stream, const uint8_t *src, const EncStream 
                         uint32_t max_stream_size, uint8_t *out, uint32_t *status);
 void launch_enc_scatter(hipStream_t stream, const uint8_t *src, const uint8_t *blob, const EncCopy *copies, uint32_t n_copies,
                         uint8_t *out);
+
+// ---- blocks with LZ sequences (encode.hip: k_enc_lz_*) ------------------------------------------
+// Every per-block buffer lies at block index * its stride; block b of the slab holds input bytes [b * kBlockMax, ...).
+constexpr uint32_t kLzMatchCap = 256;            // k_enc_lz_match extends a candidate this far; k_enc_lz_parse lengthens a selected match that reached it
+constexpr uint32_t kLzMaxSeq = 131072 / kLzMinMatch + 1;     // sequences a block can hold (21 846)
+struct LzSeq {               // one sequence: literal run, match length, distance
+    uint32_t ll, ml, dist;
+};
+struct LzBlockInfo {
+    uint32_t n_seq, n_lit;
+    uint32_t seq_bytes;      // the sequence bitstream; kLzSeqOverflow: it did not fit its scratch, the block goes without sequences
+    uint32_t pad;
+};
+constexpr uint32_t kLzSeqOverflow = 0xFFFFFFFFu;
+struct LzSeqTables {         // the predefined FSE tables, encoder side: st_x[symbol][next state] = the state of `symbol` whose
+                             // range holds `next state` (last column: any state of the symbol); nb / base per state
+    uint8_t st_ll[36][65], st_of[29][33], st_ml[53][65];
+    uint8_t nb_ll[64], nb_of[32], nb_ml[64];
+    uint16_t base_ll[64], base_of[32], base_ml[64];
+    uint32_t ll_base[36], ml_base[53];
+    uint8_t ll_bits[36], ml_bits[53];
+};
+void lz_seq_tables(LzSeqTables *t);              // synth.cpp: from seq_table_build / seq_state_for
+// match[p] = length << 17 | distance of the match found at input byte p (0: none), one word per byte of the slab
+void launch_enc_lz_match(hipStream_t stream, const uint8_t *src, uint64_t n, uint32_t n_blocks, uint32_t *match);
+// The greedy parse of every block: info, seqs (kLzMaxSeq per block) and lits (kBlockMax per block).  `exits`: one word per byte, scratch.
+void launch_enc_lz_parse(hipStream_t stream, const uint8_t *src, uint64_t n, uint32_t n_blocks, const uint32_t *match, uint32_t *exits,
+                         LzBlockInfo *info, LzSeq *seqs, uint8_t *lits);
+// k_enc_hist over the literal buffers: the four streams of info[b].n_lit bytes
+void launch_enc_lz_hist(hipStream_t stream, const uint8_t *lits, const LzBlockInfo *info, uint32_t n_blocks, uint32_t *hist);
+// the sequence bitstream of every block into bits + b * kBlockMax; info[b].seq_bytes
+void launch_enc_lz_seqbits(hipStream_t stream, const LzSeq *seqs, const LzSeqTables *tables, uint32_t n_blocks, LzBlockInfo *info, uint8_t *bits);
+// k_enc_scatter with the two further sources
+void launch_enc_scatter_lz(hipStream_t stream, const uint8_t *src, const uint8_t *blob, const uint8_t *lits, const uint8_t *bits,
+                           const EncCopy *copies, uint32_t n_copies, uint8_t *out);
 
 }  // namespace enc
 }  // namespace nafgpu

@@ -6,6 +6,11 @@
 //   k_enc_hist      per 128 KiB block: symbol counts of its four Huffman streams
 //   k_enc_streams   one workgroup per stream: the backward bit stream, built in LDS, stored to its place in the frame
 //   k_enc_scatter   block / literals headers, tree descriptions, jump tables; raw blocks' bytes
+// Blocks with LZ sequences (opts.device_lz), in front of the host's decisions:
+//   k_enc_lz_match    per 128 KiB block: the best of three earlier positions (two hash tables, one look-back) at every position
+//   k_enc_lz_parse    the greedy parse over those matches: sequences and literals per block
+//   k_enc_lz_hist     k_enc_hist over the literals
+//   k_enc_lz_seqbits  the sequences' backward bitstream with the predefined FSE tables
 // Between k_enc_hist and the last two the host decides every block from the counts (synth.cpp: plan_block), so each stream
 // and each header has its destination before its kernel starts: no kernel waits for another workgroup.
 // Plain C++ and vector stores only; the same source runs in the CPU fibre harness (tests/emu).
@@ -245,15 +250,13 @@ __device__ inline void hist_word(uint32_t *h, uint32_t w) {
 
 __device__ inline uint32_t stream_of(uint32_t i, uint32_t q) { return (i >= q) + (i >= 2 * q) + (i >= 3 * q); }
 
-__global__ __launch_bounds__(kHistThreads) void k_enc_hist(const uint8_t *src, uint64_t n, uint32_t *hist) {
+// the counts of p[0, bn) as four streams -> out[1024]
+__device__ inline void hist_block(const uint8_t *p, uint32_t bn, uint32_t *out) {
     __shared__ uint32_t s_h[kHistCopies * 1024];
     const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < kHistCopies * 1024; i += kHistThreads) s_h[i] = 0;
     __syncthreads();
-    const uint64_t p0 = static_cast<uint64_t>(blockIdx.x) * kBlockMax;
-    const uint32_t bn = n - p0 < kBlockMax ? static_cast<uint32_t>(n - p0) : kBlockMax;
     const uint32_t q = bn ? (bn + 3) / 4 : 1;
-    const uint8_t *p = src + p0;
     uint32_t *mine = s_h + (tid / (kHistThreads / kHistCopies)) * 1024;
     // bytes in front of the first 16-byte boundary and behind the last one by one, what lies between 16 at a time
     uint32_t lead = (16u - low4(p)) & 15u;
@@ -271,7 +274,7 @@ __global__ __launch_bounds__(kHistThreads) void k_enc_hist(const uint8_t *src, u
             hist_word(h, v.y);
             hist_word(h, v.z);
             hist_word(h, v.w);
-        } else {                                             // a stream ends inside (the section's last block only)
+        } else {                                             // a stream ends inside (the section's last block; literals)
             const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (uint32_t k = 0; k < 16; k++) atomicAdd(&mine[stream_of(o + k, q) * 256 + byte_of(w, k)], 1u);
@@ -282,8 +285,20 @@ __global__ __launch_bounds__(kHistThreads) void k_enc_hist(const uint8_t *src, u
         uint32_t sum = 0;
 #pragma unroll
         for (uint32_t c = 0; c < kHistCopies; c++) sum += s_h[c * 1024 + i];
-        hist[static_cast<uint64_t>(blockIdx.x) * 1024 + i] = sum;
+        out[i] = sum;
     }
+}
+
+__global__ __launch_bounds__(kHistThreads) void k_enc_hist(const uint8_t *src, uint64_t n, uint32_t *hist) {
+    const uint64_t p0 = static_cast<uint64_t>(blockIdx.x) * kBlockMax;
+    hist_block(src + p0, n - p0 < kBlockMax ? static_cast<uint32_t>(n - p0) : kBlockMax, hist + static_cast<uint64_t>(blockIdx.x) * 1024);
+}
+
+// the literals of block b: info[b].n_lit bytes at lits + b * kBlockMax
+__global__ __launch_bounds__(kHistThreads) void k_enc_lz_hist(const uint8_t *lits, const LzBlockInfo *info, uint32_t *hist) {
+    uint32_t n_lit = info[blockIdx.x].n_lit;
+    if (n_lit > kBlockMax) n_lit = kBlockMax;
+    hist_block(lits + static_cast<uint64_t>(blockIdx.x) * kBlockMax, n_lit, hist + static_cast<uint64_t>(blockIdx.x) * 1024);
 }
 
 // ======================================================================================
@@ -385,13 +400,15 @@ __global__ __launch_bounds__(kStreamThreads) void k_enc_streams(const uint8_t *s
 // k_enc_scatter
 // ======================================================================================
 // One workgroup per piece: the bytes in front of a block's streams (from the blob the host made), a raw block's bytes
-// (from the input), the "0 sequences" byte behind a compressed block, the frame header.
+// (from the input), the "0 sequences" byte behind a compressed block, the frame header; of a block with sequences its raw
+// literals (from the literal buffers) and its sequence bitstream (from k_enc_lz_seqbits' scratch).
 constexpr uint32_t kScatterThreads = 256;
 
-__global__ __launch_bounds__(kScatterThreads) void k_enc_scatter(const uint8_t *src, const uint8_t *blob, const EncCopy *copies, uint8_t *out) {
+__global__ __launch_bounds__(kScatterThreads) void k_enc_scatter(const uint8_t *src, const uint8_t *blob, const uint8_t *lits, const uint8_t *bits,
+                                                                  const EncCopy *copies, uint8_t *out) {
     const EncCopy c = copies[blockIdx.x];
     const uint32_t tid = threadIdx.x;
-    const uint8_t *s = (c.from_input ? src : blob) + c.src;
+    const uint8_t *s = (c.from_input == kCopyInput ? src : c.from_input == kCopyLiterals ? lits : c.from_input == kCopySeqBits ? bits : blob) + c.src;
     uint8_t *d = out + c.dst;
     uint32_t lead = (16u - low4(d)) & 15u;
     if (lead > c.len) lead = c.len;
@@ -411,6 +428,306 @@ __global__ __launch_bounds__(kScatterThreads) void k_enc_scatter(const uint8_t *
         }
         *reinterpret_cast<uint4 *>(d + lead + 16 * g) = make_uint4(w[0], w[1], w[2], w[3]);
     }
+}
+
+// ======================================================================================
+// k_enc_lz_match
+// ======================================================================================
+// One workgroup per block, the block walked in tiles of kLzTile positions, one lane per position.  A lane hashes the four
+// bytes at its position (the host matcher's multiplier) and tries three earlier positions:
+//   A  s_head[h]: the LATEST position in front of the tile,
+//   B  s_sub[h'][j]: the latest position in sub-tile j of the tile itself (kLzSubs sub-tiles; h': the hash's top kLzTileBits
+//      bits); a lane of sub-tile j takes the nearest non-empty sub-tile in front of its own,
+//   C  the nearest position of its own sub-tile with the same four bytes: the lanes' words lie in LDS, a lane looks back
+//      through those in front of it (at most kLzSub - 1 of them).
+// Near sources matter: their offsets take fewer bits, and in texts that count up (ids) the nearest record shares the most.
+// Both tables are filled with atomicMax of position + 1 and read only behind a barrier, so what a lane sees does not depend
+// on the order in which lanes or waves run: the frame is the same on every run and on the CPU harness.  A lane
+// extends its candidates eight bytes at a time, never past kLzMatchCap bytes (a run of one byte value would otherwise
+// make every lane walk the rest of the block) and never past the block's end; it keeps the longer match and, of two
+// equally long ones, the nearer.  No candidate lies in front of the block: blocks, chunks and slabs stay independent.
+// A lane takes kLzTile / kLzThreads positions of a tile, one in the product; the CPU harness, whose cost is the number of
+// fibres it switches at a barrier, runs the same code with 64 lanes of 16 positions.  Nothing a lane sees depends on that.
+#if defined(NAFGPU_EMU) && defined(NAFGPU_EMU_LZ_THREADS)
+constexpr uint32_t kLzThreads = NAFGPU_EMU_LZ_THREADS;      // `make emu-lz1024`: the product's shape on the harness, for a few inputs
+#elif defined(NAFGPU_EMU)
+constexpr uint32_t kLzThreads = 64;
+#else
+constexpr uint32_t kLzThreads = 1024;
+#endif
+constexpr uint32_t kLzTile = 1024, kLzPerLane = kLzTile / kLzThreads, kLzHeadBits = 14, kLzTileBits = 10, kLzSubs = 16, kLzSub = kLzTile / kLzSubs, kLzLenShift = 17;
+constexpr uint32_t kLzDistMask = (1u << kLzLenShift) - 1;
+static_assert(kBlockMax == (1u << kLzLenShift), "a distance inside the block takes kLzLenShift bits");
+static_assert(kLzMatchCap < (1u << (32 - kLzLenShift)) && kLzMatchCap % 8 == 0, "length << kLzLenShift | distance is one word");
+static_assert(kLzMaxSeq == kBlockMax / kLzMinMatch + 1, "sequences a block can hold");
+
+__device__ inline uint32_t load4(const uint8_t *p) {
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+__device__ inline uint64_t load8(const uint8_t *p) {
+    uint64_t v;
+    __builtin_memcpy(&v, p, 8);
+    return v;
+}
+
+// the number of k < max with b[from + j] == b[p + j] for all j <= k, given that it is at least len
+__device__ inline uint32_t lz_extend(const uint8_t *b, uint32_t from, uint32_t p, uint32_t len, uint32_t max) {
+    while (len + 8 <= max) {
+        const uint64_t x = load8(b + from + len) ^ load8(b + p + len);
+        if (x) return len + (static_cast<uint32_t>(__builtin_ctzll(x)) >> 3);
+        len += 8;
+    }
+    while (len < max && b[from + len] == b[p + len]) len++;
+    return len;
+}
+
+__global__ __launch_bounds__(kLzThreads) void k_enc_lz_match(const uint8_t *src, uint64_t n, uint32_t *match) {
+    __shared__ uint32_t s_head[1u << kLzHeadBits];        // position + 1; 0: none
+    __shared__ uint32_t s_sub[kLzSubs << kLzTileBits];    // position + 1; 0: none
+    __shared__ uint32_t s_val[kLzTile];                   // the four bytes at the tile's positions
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < (1u << kLzHeadBits); i += kLzThreads) s_head[i] = 0;
+    for (uint32_t i = tid; i < (kLzSubs << kLzTileBits); i += kLzThreads) s_sub[i] = 0;
+    __syncthreads();
+    const uint64_t p0 = static_cast<uint64_t>(blockIdx.x) * kBlockMax;
+    const uint32_t bn = n - p0 < kBlockMax ? static_cast<uint32_t>(n - p0) : kBlockMax;
+    const uint8_t *b = src + p0;
+    uint32_t *m = match + p0;
+    for (uint32_t tile0 = 0; tile0 < bn; tile0 += kLzTile) {
+        uint32_t h[kLzPerLane], h2[kLzPerLane], val[kLzPerLane], cand_a[kLzPerLane], cand_b[kLzPerLane], cand_c[kLzPerLane];
+#pragma unroll
+        for (uint32_t k = 0; k < kLzPerLane; k++) {
+            const uint32_t i = tid + k * kLzThreads, p = tile0 + i;
+            h[k] = h2[k] = val[k] = cand_a[k] = cand_b[k] = cand_c[k] = 0;
+            if (p + kLzMinMatch <= bn) {                    // a match can start here
+                val[k] = load4(b + p);
+                s_val[i] = val[k];
+                const uint32_t prod = val[k] * 2654435761u;
+                h[k] = prod >> (32 - kLzHeadBits);
+                h2[k] = (prod >> (32 - kLzTileBits)) * kLzSubs;
+                cand_a[k] = s_head[h[k]];
+                atomicMax(&s_sub[h2[k] + i / kLzSub], p + 1);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < kLzPerLane; k++) {
+            const uint32_t i = tid + k * kLzThreads, sub = i / kLzSub;
+            if (tile0 + i + kLzMinMatch > bn) continue;
+            for (uint32_t j = sub; j-- > 0 && !cand_b[k];) cand_b[k] = s_sub[h2[k] + j];
+            for (uint32_t q = i; q-- > sub * kLzSub && !cand_c[k];)
+                if (s_val[q] == val[k]) cand_c[k] = tile0 + q + 1;
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < kLzPerLane; k++) {
+            const uint32_t i = tid + k * kLzThreads, p = tile0 + i;
+            uint32_t best = 0, from = 0;
+            if (p + kLzMinMatch <= bn) {
+                s_sub[h2[k] + i / kLzSub] = 0;              // the writers clear it for the next tile
+                atomicMax(&s_head[h[k]], p + 1);
+                const uint32_t max = bn - p < kLzMatchCap ? bn - p : kLzMatchCap;
+                if (cand_a[k]) {
+                    const uint32_t len = lz_extend(b, cand_a[k] - 1, p, 0, max);
+                    if (len >= kLzMinMatch) best = len, from = cand_a[k] - 1;
+                }
+                if (cand_b[k]) {                            // nearer than A: it wins a tie
+                    const uint32_t len = lz_extend(b, cand_b[k] - 1, p, 0, max);
+                    if (len >= kLzMinMatch && len >= best) best = len, from = cand_b[k] - 1;
+                }
+                if (cand_c[k]) {                            // the nearest of the three
+                    const uint32_t len = lz_extend(b, cand_c[k] - 1, p, 4, max);
+                    if (len >= kLzMinMatch && len >= best) best = len, from = cand_c[k] - 1;
+                }
+            }
+            if (p < bn) m[p] = best ? (best << kLzLenShift) | (p - from) : 0u;
+        }
+        __syncthreads();
+    }
+}
+
+// ======================================================================================
+// k_enc_lz_parse
+// ======================================================================================
+// The greedy parse is the chain  next(p) = p + length(p) if a match was found at p, else p + 1,  from the block's first
+// byte; only positions on the chain emit.  next(p) > p, so the block is cut into kLzSegs segments, one per lane (16 per
+// lane on the CPU harness):
+//   A  every lane goes through its segment from the back: exit(p) = next(p) if that leaves the segment, else
+//      exit(next(p)) -- where the chain leaves the segment when it enters it at p, for every p, without knowing the entry.
+//      Beside it: the first position on the way whose match reached kLzMatchCap.
+//   B  lane 0 goes from segment to segment (at most kLzSegs steps), noting each segment's entry.  A capped match on
+//      the chain is lengthened here, to the block's end at the most: only selected matches are, so all of them together
+//      compare less than the block's bytes.  The final length replaces that position's exit word.
+//   C  every lane walks its segment from its entry and counts sequences and literals; lane 0 turns the counts into offsets,
+//      and into the literals pending in front of each segment;
+//   E  the same walk writes the sequences and copies the literals.
+constexpr uint32_t kLzSegs = 1024, kLzSeg = kBlockMax / kLzSegs;      // of 128 positions
+constexpr uint32_t kLzExitMask = (1u << 18) - 1, kLzHasCap = 1u << 18, kLzCapShift = 19, kLzNone = 0xFFFFFFFFu;
+
+// the length of the match the chain takes at p (0: a literal)
+__device__ inline uint32_t lz_taken(const uint32_t *m, const uint32_t *ex, uint32_t p, uint32_t bn) {
+    const uint32_t len = m[p] >> kLzLenShift;
+    return len == kLzMatchCap && p + len < bn ? ex[p] : len;
+}
+
+__global__ __launch_bounds__(kLzThreads) void k_enc_lz_parse(const uint8_t *src, uint64_t n, const uint32_t *match, uint32_t *exits,
+                                                              LzBlockInfo *info, LzSeq *seqs, uint8_t *lits) {
+    __shared__ uint32_t s_entry[kLzSegs], s_seq[kLzSegs], s_lit[kLzSegs], s_run[kLzSegs];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t p0 = static_cast<uint64_t>(blockIdx.x) * kBlockMax;
+    const uint32_t bn = n - p0 < kBlockMax ? static_cast<uint32_t>(n - p0) : kBlockMax;
+    const uint8_t *b = src + p0;
+    const uint32_t *m = match + p0;
+    uint32_t *ex = exits + p0;
+    auto seg_end_of = [bn](uint32_t seg0) { return seg0 >= bn ? seg0 : (bn - seg0 < kLzSeg ? bn : seg0 + kLzSeg); };
+    for (uint32_t sg = tid; sg < kLzSegs; sg += kLzThreads) {   // A
+        const uint32_t seg0 = sg * kLzSeg, seg_end = seg_end_of(seg0);
+        s_entry[sg] = kLzNone;
+        for (uint32_t p = seg_end; p-- > seg0;) {
+            const uint32_t len = m[p] >> kLzLenShift, nx = p + (len ? len : 1u);
+            uint32_t v = nx >= seg_end ? nx : ex[nx];
+            if (len == kLzMatchCap && nx < bn) v = kLzHasCap | ((p - seg0) << kLzCapShift);
+            ex[p] = v;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {                                         // B
+        uint32_t p = 0;
+        while (p < bn) {
+            const uint32_t seg = p / kLzSeg, v = ex[p];
+            if (s_entry[seg] == kLzNone) s_entry[seg] = p;
+            if (v & kLzHasCap) {
+                const uint32_t c = seg * kLzSeg + (v >> kLzCapShift);
+                const uint32_t len = lz_extend(b, c - (m[c] & kLzDistMask), c, kLzMatchCap, bn - c);
+                ex[c] = len;
+                p = c + len;
+            } else {
+                p = v & kLzExitMask;
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t sg = tid; sg < kLzSegs; sg += kLzThreads) {   // C; trail: literals behind the segment's last match
+        const uint32_t entry = s_entry[sg], seg_end = seg_end_of(sg * kLzSeg);
+        uint32_t n_seq = 0, n_lit = 0, trail = 0;
+        if (entry != kLzNone)
+            for (uint32_t p = entry; p < seg_end;) {
+                const uint32_t len = lz_taken(m, ex, p, bn);
+                if (len) n_seq++, trail = 0, p += len;
+                else n_lit++, trail++, p++;
+            }
+        s_seq[sg] = n_seq;
+        s_lit[sg] = n_lit;
+        s_run[sg] = trail;
+    }
+    __syncthreads();
+    if (tid == 0) {                                         // exclusive sums; s_run: the literals pending in front of the segment
+        uint32_t seq_at = 0, lit_at = 0, run = 0;
+        for (uint32_t k = 0; k < kLzSegs; k++) {
+            const uint32_t ns = s_seq[k], nl = s_lit[k], tr = s_run[k];
+            s_seq[k] = seq_at;
+            s_lit[k] = lit_at;
+            s_run[k] = run;
+            seq_at += ns;
+            lit_at += nl;
+            run = ns ? tr : run + nl;
+        }
+        info[blockIdx.x] = LzBlockInfo{seq_at, lit_at, 0, 0};
+    }
+    __syncthreads();
+    for (uint32_t sg = tid; sg < kLzSegs; sg += kLzThreads) {   // E
+        const uint32_t entry = s_entry[sg], seg_end = seg_end_of(sg * kLzSeg);
+        if (entry == kLzNone) continue;
+        LzSeq *sq = seqs + static_cast<uint64_t>(blockIdx.x) * kLzMaxSeq + s_seq[sg];
+        uint8_t *lt = lits + p0 + s_lit[sg];
+        uint32_t run = s_run[sg];
+        for (uint32_t p = entry; p < seg_end;) {
+            const uint32_t len = lz_taken(m, ex, p, bn);
+            if (len) {
+                *sq++ = LzSeq{run, len, m[p] & kLzDistMask};
+                run = 0;
+                p += len;
+            } else {
+                *lt++ = b[p++];
+                run++;
+            }
+        }
+    }
+}
+
+// ======================================================================================
+// k_enc_lz_seqbits
+// ======================================================================================
+// One workgroup of one wave per block, so that the blocks spread over the CUs; its lane 0 walks a dependent chain over the
+// block's sequences, k_seq_states the other way round (the other lanes only help to fill the tables).  What the decoder
+// reads first is written last (sequences_section, synth.cpp): from the last sequence to the first, the state updates that
+// lead to the sequence behind (OF, ML, LL), then the extra bits LL, ML, OF; at the end the first sequence's states ML,
+// OF, LL and the end mark.  Every offset is a new offset: Offset_Value = distance + 3.
+constexpr uint32_t kSeqBitsThreads = 64, kSeqBitsMargin = 32;
+static_assert(sizeof(LzSeqTables) % 4 == 0, "copied to LDS as words");
+
+struct BitOut {
+    uint32_t *w;
+    uint32_t at = 0, nb = 0;
+    uint64_t acc = 0;
+    __device__ inline void put(uint32_t v, uint32_t bits) {          // bits <= 17
+        acc |= static_cast<uint64_t>(v) << nb;
+        nb += bits;
+        if (nb >= 32) {
+            w[at++] = static_cast<uint32_t>(acc);
+            acc >>= 32;
+            nb -= 32;
+        }
+    }
+};
+
+__global__ __launch_bounds__(kSeqBitsThreads) void k_enc_lz_seqbits(const LzSeq *seqs, const LzSeqTables *tables, uint32_t n_blocks,
+                                                                     LzBlockInfo *info, uint8_t *bits) {
+    __shared__ LzSeqTables s_t;
+    for (uint32_t i = threadIdx.x; i < sizeof(LzSeqTables) / 4; i += kSeqBitsThreads)
+        reinterpret_cast<uint32_t *>(&s_t)[i] = reinterpret_cast<const uint32_t *>(tables)[i];
+    __syncthreads();
+    const uint32_t blk = blockIdx.x;
+    if (threadIdx.x || blk >= n_blocks) return;
+    const uint32_t n_seq = info[blk].n_seq;
+    if (!n_seq) return;
+    const LzSeq *sq = seqs + static_cast<uint64_t>(blk) * kLzMaxSeq;
+    BitOut o;
+    o.w = reinterpret_cast<uint32_t *>(bits + static_cast<uint64_t>(blk) * kBlockMax);
+    uint32_t s_ll = 64, s_of = 32, s_ml = 64;               // the states of the sequence behind; at first: any
+    for (uint32_t i = n_seq; i-- > 0;) {
+        if (o.at * 4 + kSeqBitsMargin > kBlockMax) {        // larger than the block itself: it could not have won
+            info[blk].seq_bytes = kLzSeqOverflow;
+            return;
+        }
+        const LzSeq q = sq[i];
+        const uint32_t ofv = q.dist + 3, co = 31u - static_cast<uint32_t>(__builtin_clz(ofv));
+        uint32_t cl = q.ll, cm = q.ml - 3;
+        if (cl >= 16)
+            for (cl = 35; q.ll < s_t.ll_base[cl]; cl--) {}
+        if (cm >= 32)
+            for (cm = 52; q.ml < s_t.ml_base[cm]; cm--) {}
+        const uint32_t t_ll = s_t.st_ll[cl][s_ll], t_of = s_t.st_of[co][s_of], t_ml = s_t.st_ml[cm][s_ml];
+        if (i + 1 < n_seq) {
+            o.put(s_of - s_t.base_of[t_of], s_t.nb_of[t_of]);
+            o.put(s_ml - s_t.base_ml[t_ml], s_t.nb_ml[t_ml]);
+            o.put(s_ll - s_t.base_ll[t_ll], s_t.nb_ll[t_ll]);
+        }
+        o.put(q.ll - s_t.ll_base[cl], s_t.ll_bits[cl]);
+        o.put(q.ml - s_t.ml_base[cm], s_t.ml_bits[cm]);
+        o.put(ofv - (1u << co), co);
+        s_ll = t_ll;
+        s_of = t_of;
+        s_ml = t_ml;
+    }
+    o.put(s_ml, 6);
+    o.put(s_of, 5);
+    o.put(s_ll, 6);
+    o.put(1, 1);                                            // end mark
+    if (o.nb) o.w[o.at] = static_cast<uint32_t>(o.acc);
+    info[blk].seq_bytes = o.at * 4 + (o.nb + 7) / 8;
 }
 
 uint32_t grid_for(uint64_t items, uint32_t per_block) {
@@ -483,7 +800,34 @@ void launch_enc_streams(hipStream_t stream, const uint8_t *src, const EncStream 
 void launch_enc_scatter(hipStream_t stream, const uint8_t *src, const uint8_t *blob, const EncCopy *copies, uint32_t n_copies,
                         uint8_t *out) {
     if (!n_copies) return;
-    hipLaunchKernelGGL(k_enc_scatter, dim3(n_copies), dim3(kScatterThreads), 0, stream, src, blob, copies, out);
+    launch_enc_scatter_lz(stream, src, blob, nullptr, nullptr, copies, n_copies, out);
+}
+
+void launch_enc_scatter_lz(hipStream_t stream, const uint8_t *src, const uint8_t *blob, const uint8_t *lits, const uint8_t *bits,
+                           const EncCopy *copies, uint32_t n_copies, uint8_t *out) {
+    if (!n_copies) return;
+    hipLaunchKernelGGL(k_enc_scatter, dim3(n_copies), dim3(kScatterThreads), 0, stream, src, blob, lits, bits, copies, out);
+}
+
+void launch_enc_lz_match(hipStream_t stream, const uint8_t *src, uint64_t n, uint32_t n_blocks, uint32_t *match) {
+    if (!n_blocks) return;
+    hipLaunchKernelGGL(k_enc_lz_match, dim3(n_blocks), dim3(kLzThreads), 0, stream, src, n, match);
+}
+
+void launch_enc_lz_parse(hipStream_t stream, const uint8_t *src, uint64_t n, uint32_t n_blocks, const uint32_t *match, uint32_t *exits,
+                         LzBlockInfo *info, LzSeq *seqs, uint8_t *lits) {
+    if (!n_blocks) return;
+    hipLaunchKernelGGL(k_enc_lz_parse, dim3(n_blocks), dim3(kLzThreads), 0, stream, src, n, match, exits, info, seqs, lits);
+}
+
+void launch_enc_lz_hist(hipStream_t stream, const uint8_t *lits, const LzBlockInfo *info, uint32_t n_blocks, uint32_t *hist) {
+    if (!n_blocks) return;
+    hipLaunchKernelGGL(k_enc_lz_hist, dim3(n_blocks), dim3(kHistThreads), 0, stream, lits, info, hist);
+}
+
+void launch_enc_lz_seqbits(hipStream_t stream, const LzSeq *seqs, const LzSeqTables *tables, uint32_t n_blocks, LzBlockInfo *info, uint8_t *bits) {
+    if (!n_blocks) return;
+    hipLaunchKernelGGL(k_enc_lz_seqbits, dim3(n_blocks), dim3(kSeqBitsThreads), 0, stream, seqs, tables, n_blocks, info, bits);
 }
 
 }  // namespace enc

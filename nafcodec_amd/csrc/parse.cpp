@@ -242,7 +242,7 @@ int nafgpu_encode_text(const uint8_t *text, uint64_t n, const nafgpu_parse_opts 
     if (opts->sequence_type > 3) return fail_c(err, Failure::make(NAFGPU_E_INVALID_ARG, "invalid encoder options"));
     if (!enc::mask_opts_ok(*opts))
         return fail_c(err, Failure::make(NAFGPU_E_INVALID_ARG, "mask needs a nucleotide sequence: sequence set, sequence_type dna or rna"));
-    if (opts->compression_level != 1 && opts->compression_level != 2)
+    if (opts->compression_level != 1 && opts->compression_level != 2 && !opts->device_lz)
         return fail_c(err, Failure::make(NAFGPU_E_INVALID_ARG, "the device encoder writes literal-only blocks: compression_level 1 or 2"));
     nafgpu_parse_opts po;
     nafgpu_parse_opts_default(&po);

@@ -467,6 +467,106 @@ void emit_block(const BlockPlan &p, const uint8_t *data, std::vector<uint8_t> &o
     out.push_back(0x00);                                         // Number_of_Sequences = 0
 }
 
+// The Literals_Section of a block WITH sequences, from the counts of its `n` literal bytes (streams as in count_block; not
+// read when n < 256): raw under 256 bytes, RLE for one byte value, else Huffman with four streams -- a new tree or *prev's,
+// whichever costs less -- unless that gains nothing.  plan->head: the literals header and what follows it in front of the
+// streams (RLE: the byte; Huffman: the tree of a new table, the jump table); plan->total: the section's size.  *prev is
+// only read: the caller replaces it by plan->code when it emits a block whose mode is kHufNew.
+void plan_literals(const uint32_t counts[4][256], size_t n, const HufCode *prev, BlockPlan *plan) {
+    BlockPlan &p = *plan;
+    p.head.clear();
+    p.n = n;
+    auto raw = [&]() {
+        p.mode = kRaw;
+        p.head.clear();
+        if (n < 32) {
+            p.head.push_back(static_cast<uint8_t>(n << 3));
+        } else if (n < 4096) {
+            const uint32_t v = (static_cast<uint32_t>(n) << 4) | (1u << 2);
+            p.head.push_back(v & 0xFF);
+            p.head.push_back(v >> 8);
+        } else {
+            const uint32_t v = (static_cast<uint32_t>(n) << 4) | (3u << 2);
+            p.head.push_back(v & 0xFF);
+            p.head.push_back((v >> 8) & 0xFF);
+            p.head.push_back(v >> 16);
+        }
+        p.total = p.head.size() + n;
+    };
+    if (n < 256) return raw();
+    uint32_t count[256];
+    int first = -1;
+    for (int s = 0; s < 256; s++) {
+        count[s] = counts[0][s] + counts[1][s] + counts[2][s] + counts[3][s];
+        if (count[s] && first < 0) first = s;
+    }
+    if (count[first] == n) {                                     // RLE literals
+        const uint32_t v = (static_cast<uint32_t>(n) << 4) | (3u << 2) | 1u;
+        p.mode = kRle;
+        p.head.push_back(v & 0xFF);
+        p.head.push_back((v >> 8) & 0xFF);
+        p.head.push_back(v >> 16);
+        p.head.push_back(static_cast<uint8_t>(first));
+        p.total = 4;
+        return;
+    }
+    HufCode cur{};
+    std::vector<uint8_t> tree;
+    bool have_new = build_lengths(count, cur.len);
+    if (have_new) {
+        assign_codes(&cur);
+        have_new = cur.valid && write_weights(cur.weight, cur.max_sym, tree);
+    }
+    uint64_t cost_new = UINT64_MAX, cost_old = UINT64_MAX;
+    if (have_new) {
+        cost_new = tree.size() * 8;
+        for (int k = 0; k < 256; k++) cost_new += static_cast<uint64_t>(count[k]) * cur.len[k];
+    }
+    if (prev->valid) {
+        cost_old = 0;
+        for (int k = 0; k < 256; k++) {
+            if (!count[k]) continue;
+            if (!prev->len[k]) {
+                cost_old = UINT64_MAX;
+                break;
+            }
+            cost_old += static_cast<uint64_t>(count[k]) * prev->len[k];
+        }
+    }
+    if (cost_new == UINT64_MAX && cost_old == UINT64_MAX) return raw();
+    const bool treeless = cost_old <= cost_new;
+    const HufCode &h = treeless ? *prev : cur;
+    size_t comp = (treeless ? 0 : tree.size()) + 6;              // tree + jump table + streams
+    for (int k = 0; k < 4; k++) {
+        uint64_t bits = 0;
+        for (int s = 0; s < 256; s++) bits += static_cast<uint64_t>(counts[k][s]) * h.len[s];
+        p.stream_size[k] = static_cast<uint32_t>(bits / 8 + 1);
+        if (k < 3 && p.stream_size[k] > 0xFFFF) return raw();
+        comp += p.stream_size[k];
+    }
+    if (comp >= n) return raw();
+    const uint32_t type = treeless ? 3u : 2u;
+    if (n <= 1023 && comp <= 1023) {
+        const uint32_t v = type | (1u << 2) | (static_cast<uint32_t>(n) << 4) | (static_cast<uint32_t>(comp) << 14);
+        for (int k = 0; k < 3; k++) p.head.push_back((v >> (8 * k)) & 0xFF);
+    } else if (n <= 16383 && comp <= 16383) {
+        const uint32_t v = type | (2u << 2) | (static_cast<uint32_t>(n) << 4) | (static_cast<uint32_t>(comp) << 18);
+        for (int k = 0; k < 4; k++) p.head.push_back((v >> (8 * k)) & 0xFF);
+    } else {
+        const uint64_t v = type | (3u << 2) | (static_cast<uint64_t>(n) << 4) | (static_cast<uint64_t>(comp) << 22);
+        for (int k = 0; k < 5; k++) p.head.push_back((v >> (8 * k)) & 0xFF);
+    }
+    const size_t lhn = p.head.size();
+    if (!treeless) p.head.insert(p.head.end(), tree.begin(), tree.end());
+    for (int k = 0; k < 3; k++) {
+        p.head.push_back(p.stream_size[k] & 0xFF);
+        p.head.push_back(static_cast<uint8_t>(p.stream_size[k] >> 8));
+    }
+    p.mode = treeless ? kHufTreeless : kHufNew;
+    p.code = h;
+    p.total = lhn + comp;
+}
+
 }  // namespace enc
 }  // namespace nafgpu
 namespace {
@@ -730,90 +830,23 @@ extern "C" void nafgpu_synth_free(nafgpu_synth_archive *a) {
 // ======================================================================================
 namespace {
 
-// Literals_Section (RFC 8878 3.1.1.3.1) of `n` bytes: Huffman with four streams (new tree, or the previous block's), RLE, or raw.
+// Literals_Section (RFC 8878 3.1.1.3.1) of `n` bytes: what plan_literals decides, then the bytes (raw) or the four streams.
 // *used_new: the section carries a new tree (the caller makes it the previous one if the block is emitted).
 void literals_section(const uint8_t *data, size_t n, const HufCode *prev, HufCode *cur, bool *used_new, std::vector<uint8_t> &out) {
-    *used_new = false;
-    auto raw = [&]() {
-        if (n < 32) {
-            out.push_back(static_cast<uint8_t>(n << 3));
-        } else if (n < 4096) {
-            const uint32_t v = (static_cast<uint32_t>(n) << 4) | (1u << 2);
-            out.push_back(v & 0xFF);
-            out.push_back(v >> 8);
-        } else {
-            const uint32_t v = (static_cast<uint32_t>(n) << 4) | (3u << 2);
-            out.push_back(v & 0xFF);
-            out.push_back((v >> 8) & 0xFF);
-            out.push_back(v >> 16);
-        }
-        out.insert(out.end(), data, data + n);
-    };
-    if (n < 256) return raw();
-    uint32_t count[256] = {0};
-    for (size_t i = 0; i < n; i++) count[data[i]]++;
-    if (count[data[0]] == n) {                                   // RLE literals
-        const uint32_t v = (static_cast<uint32_t>(n) << 4) | (3u << 2) | 1u;
-        out.push_back(v & 0xFF);
-        out.push_back((v >> 8) & 0xFF);
-        out.push_back(v >> 16);
-        out.push_back(data[0]);
-        return;
-    }
-    std::vector<uint8_t> tree;
-    bool have_new = build_lengths(count, cur->len);
-    if (have_new) {
-        assign_codes(cur);
-        have_new = cur->valid && write_weights(cur->weight, cur->max_sym, tree);
-    }
-    uint64_t cost_new = UINT64_MAX, cost_old = UINT64_MAX;
-    if (have_new) {
-        cost_new = tree.size() * 8;
-        for (int k = 0; k < 256; k++) cost_new += static_cast<uint64_t>(count[k]) * cur->len[k];
-    }
-    if (prev->valid) {
-        cost_old = 0;
-        for (int k = 0; k < 256; k++) {
-            if (!count[k]) continue;
-            if (!prev->len[k]) {
-                cost_old = UINT64_MAX;
-                break;
-            }
-            cost_old += static_cast<uint64_t>(count[k]) * prev->len[k];
-        }
-    }
-    if (cost_new == UINT64_MAX && cost_old == UINT64_MAX) return raw();
-    const bool treeless = cost_old <= cost_new;
-    const HufCode &h = treeless ? *prev : *cur;
-    std::vector<uint8_t> body;
-    if (!treeless) body = tree;
+    uint32_t counts[4][256];
+    if (n >= 256) count_block(data, n, counts);
+    BlockPlan p;
+    plan_literals(counts, n, prev, &p);
+    out.insert(out.end(), p.head.begin(), p.head.end());
+    *used_new = p.mode == kHufNew;
+    if (p.mode == kRaw) out.insert(out.end(), data, data + n);
+    if (p.mode != kHufNew && p.mode != kHufTreeless) return;
+    if (*used_new) *cur = p.code;
     const size_t q = (n + 3) / 4;
-    std::vector<uint8_t> st[4];
-    encode_stream(h, data, q, st[0]);
-    encode_stream(h, data + q, q, st[1]);
-    encode_stream(h, data + 2 * q, q, st[2]);
-    encode_stream(h, data + 3 * q, n - 3 * q, st[3]);
-    for (int k = 0; k < 3; k++) {
-        if (st[k].size() > 0xFFFF) return raw();
-        body.push_back(st[k].size() & 0xFF);
-        body.push_back(static_cast<uint8_t>(st[k].size() >> 8));
-    }
-    for (int k = 0; k < 4; k++) body.insert(body.end(), st[k].begin(), st[k].end());
-    const size_t comp = body.size();
-    if (comp >= n) return raw();
-    const uint32_t type = treeless ? 3u : 2u;
-    if (n <= 1023 && comp <= 1023) {
-        const uint32_t v = type | (1u << 2) | (static_cast<uint32_t>(n) << 4) | (static_cast<uint32_t>(comp) << 14);
-        for (int k = 0; k < 3; k++) out.push_back((v >> (8 * k)) & 0xFF);
-    } else if (n <= 16383 && comp <= 16383) {
-        const uint32_t v = type | (2u << 2) | (static_cast<uint32_t>(n) << 4) | (static_cast<uint32_t>(comp) << 18);
-        for (int k = 0; k < 4; k++) out.push_back((v >> (8 * k)) & 0xFF);
-    } else {
-        const uint64_t v = type | (3u << 2) | (static_cast<uint64_t>(n) << 4) | (static_cast<uint64_t>(comp) << 22);
-        for (int k = 0; k < 5; k++) out.push_back((v >> (8 * k)) & 0xFF);
-    }
-    out.insert(out.end(), body.begin(), body.end());
-    *used_new = !treeless;
+    encode_stream(p.code, data, q, out);
+    encode_stream(p.code, data + q, q, out);
+    encode_stream(p.code, data + 2 * q, q, out);
+    encode_stream(p.code, data + 3 * q, n - 3 * q, out);
 }
 
 // The predefined FSE tables of the sequence codes (RFC 8878 3.1.1.3.2.2), as the DECODER builds them; encoding walks them
@@ -886,6 +919,36 @@ int ml_code(uint32_t ml) {
     return 0;
 }
 
+}  // namespace
+namespace nafgpu {
+namespace enc {
+// the three predefined tables in the encoder's orientation, for k_enc_lz_seqbits
+void lz_seq_tables(LzSeqTables *t) {
+    std::memset(t, 0xFF, sizeof *t);
+    SeqTable tl, to, tm;
+    seq_table_build(kEncLL, 36, 6, &tl);
+    seq_table_build(kEncOF, 29, 5, &to);
+    seq_table_build(kEncML, 53, 6, &tm);
+    for (int s = 0; s < 36; s++)
+        for (int next = 0; next <= 64; next++) t->st_ll[s][next] = static_cast<uint8_t>(seq_state_for(tl, s, next < 64 ? next : -1));
+    for (int s = 0; s < 29; s++)
+        for (int next = 0; next <= 32; next++) t->st_of[s][next] = static_cast<uint8_t>(seq_state_for(to, s, next < 32 ? next : -1));
+    for (int s = 0; s < 53; s++)
+        for (int next = 0; next <= 64; next++) t->st_ml[s][next] = static_cast<uint8_t>(seq_state_for(tm, s, next < 64 ? next : -1));
+    for (int i = 0; i < 64; i++) {
+        t->nb_ll[i] = tl.nb[i], t->base_ll[i] = tl.base[i];
+        t->nb_ml[i] = tm.nb[i], t->base_ml[i] = tm.base[i];
+    }
+    for (int i = 0; i < 32; i++) t->nb_of[i] = to.nb[i], t->base_of[i] = to.base[i];
+    std::memcpy(t->ll_base, kEncLLBase, sizeof t->ll_base);
+    std::memcpy(t->ll_bits, kEncLLBits, sizeof t->ll_bits);
+    std::memcpy(t->ml_base, kEncMLBase, sizeof t->ml_base);
+    std::memcpy(t->ml_bits, kEncMLBits, sizeof t->ml_bits);
+}
+}  // namespace enc
+}  // namespace nafgpu
+namespace {
+
 // Sequences_Section with the three predefined tables: header, then the backward bitstream
 void sequences_section(const std::vector<LzSeq> &seqs, std::vector<uint8_t> &out) {
     static const SeqTable *tabs = [] {
@@ -943,7 +1006,7 @@ void sequences_section(const std::vector<LzSeq> &seqs, std::vector<uint8_t> &out
     out.insert(out.end(), bits.bytes.begin(), bits.bytes.end());
 }
 
-constexpr uint32_t kLzHashBits = 17, kLzMinMatch = 6, kLzWindow = 1u << 20;
+constexpr uint32_t kLzHashBits = 17, kLzWindow = 1u << 20;       // (kLzMinMatch: encode.h)
 // One block of [data + b0, data + b0 + n) with greedy hash matching against everything since `chunk0` (and at most the window).
 void encode_block_lz(const uint8_t *data, size_t chunk0, size_t b0, size_t n, bool last, HufCode *prev, std::vector<uint32_t> &head,
                      std::vector<uint8_t> &out) {
@@ -1247,13 +1310,14 @@ extern "C" int nafgpu_encoder_finish(nafgpu_encoder *e, const uint8_t **bytes, u
         std::vector<uint8_t> &o = e->archive;
         put_archive_head(o, e->opt, e->n_records);
         nafgpu::Failure dev_fail;
+        const bool lz = e->opt.compression_level == 0 || e->opt.compression_level >= 3;
         auto block = [&](const std::vector<uint8_t> &data, uint64_t original) {      // write_block!, mod.rs:349-367
             std::vector<uint8_t> frame;
             if (e->device >= -1) {
-                if (dev_fail.ok()) dev_fail = compress_section_device(data.data(), data.size(), false, e->device, e->opt.threads, frame, nullptr);
+                if (dev_fail.ok()) dev_fail = compress_section_device(data.data(), data.size(), false, e->device, e->opt.threads, lz, frame, nullptr);
                 if (!dev_fail.ok()) return;
             } else {
-                compress_section(data, e->opt.threads, e->opt.compression_level == 0 || e->opt.compression_level >= 3, frame);
+                compress_section(data, e->opt.threads, lz, frame);
             }
             put_varint(o, original);
             put_varint(o, frame.size());
@@ -1286,7 +1350,8 @@ extern "C" int nafgpu_encoder_finish(nafgpu_encoder *e, const uint8_t **bytes, u
 
 extern "C" int nafgpu_encoder_set_device(nafgpu_encoder *e, int device) {
     if (!e || device < -1 || e->finished) return NAFGPU_E_INVALID_ARG;
-    if (e->opt.compression_level != 1 && e->opt.compression_level != 2) return NAFGPU_E_INVALID_ARG;   // blocks with LZ sequences are host-only
+    if (e->opt.compression_level != 1 && e->opt.compression_level != 2 && !e->opt.device_lz)
+        return NAFGPU_E_INVALID_ARG;                             // blocks with LZ sequences on the device: opts.device_lz
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return NAFGPU_E_DEVICE;
     if (device >= count) return NAFGPU_E_INVALID_ARG;

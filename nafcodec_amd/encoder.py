@@ -2,7 +2,8 @@
 (nafcodec-py/nafcodec/lib.pyi:69-87, lib.rs:463-600; the Rust side: encoder/mod.rs:46-384).  Host code, like the
 reference's; every section is written as Huffman-literal Zstandard blocks (include/nafgpu.h: Encoder).  With `device=` the
 sections of compression levels 1 and 2 are compressed by the HIP kernels instead (same bytes), and `encode_device` writes
-an archive from records that are already in HBM.  `parse_text` makes such records from FASTA / FASTQ text on the device, and
+an archive from records that are already in HBM.  `device_lz=True` lets those device calls take the levels with LZ matches
+(0 and >= 3) as well: the matches are found on the GPU, and the archive is a valid one of its own, not the host's bytes.  `parse_text` makes such records from FASTA / FASTQ text on the device, and
 `encode_text` is both in one call: file in, archive out.  `mask=True` (no counterpart in the reference, whose mask writer is
 commented out) accepts lower-case nucleotides and writes their runs as a Mask section."""
 import ctypes
@@ -17,7 +18,7 @@ class Encoder:
     """lib.pyi:69-87.  `file` is a path or a binary file-like object; the archive is written by close()."""
 
     def __init__(self, file, sequence_type="dna", *, id=False, comment=False, sequence=False, quality=False,
-                 compression_level=0, device=None, mask=False, _lib=None):
+                 compression_level=0, device=None, mask=False, device_lz=False, _lib=None):
         if sequence_type not in SEQUENCE_TYPES:
             raise ValueError("expected 'dna', 'rna', 'protein' or 'text', got %r" % (sequence_type,))   # lib.rs:487-495
         _check_mask(mask, sequence_type, sequence)
@@ -30,17 +31,19 @@ class Encoder:
         self._lib.c.nafgpu_encoder_opts_default(SEQUENCE_TYPES.index(sequence_type), byref(opts))
         opts.id, opts.comment, opts.sequence, opts.quality = map(int, (id, comment, sequence, quality))
         opts.compression_level, opts.mask = int(compression_level), int(bool(mask))
+        opts.device_lz = int(bool(device_lz))                # read by the device calls only
         h, err = c_void_p(), _ffi.Error()
         if self._lib.c.nafgpu_encoder_new(byref(opts), byref(h), byref(err)) != _ffi.OK:
             raise _ffi.NafError.from_c(err)
         self._h = h
-        if device is not None:                               # an int: the sections are compressed on that GPU (levels 1 and 2)
+        if device is not None:                               # an int: the sections are compressed on that GPU (levels 1 and 2; device_lz: any)
             rc = self._lib.c.nafgpu_encoder_set_device(h, int(device))
             if rc != _ffi.OK:
                 self._h = None
                 self._lib.c.nafgpu_encoder_free(h)
                 if rc == _ffi.E_INVALID_ARG:
-                    raise ValueError("device encoding writes literal-only blocks: compression_level 1 or 2, and an existing device")
+                    raise ValueError("device encoding writes literal-only blocks: compression_level 1 or 2 (or device_lz=True), "
+                                     "and an existing device")
                 raise _ffi.NafError(rc, message="no usable HIP device")
         if isinstance(file, (str, bytes, os.PathLike)):      # fail now, as the reference does when it creates the file
             self._out = open_binary(file)
@@ -106,9 +109,10 @@ class Encoder:
             self._h = None
 
 
-def zstd_compress(data, device=0, _lib=None):
-    """One section's bytes -> the magicless Zstandard frame the Encoder writes for it at compression_level 1, on the GPU."""
-    return (_lib or _ffi.default()).zstd_compress(bytes(data), device)
+def zstd_compress(data, device=0, lz=False, _lib=None):
+    """One section's bytes -> the magicless Zstandard frame the Encoder writes for it at compression_level 1, on the GPU.
+    `lz=True`: a frame of blocks with LZ sequences instead, the device matcher's own (what device_lz=True writes)."""
+    return (_lib or _ffi.default()).zstd_compress(bytes(data), device, lz)
 
 
 def _check_mask(mask, sequence_type, sequence):
@@ -117,8 +121,9 @@ def _check_mask(mask, sequence_type, sequence):
 
 
 def encode_device(result, *, sequence_type="dna", id=False, comment=False, sequence=False, quality=False, compression_level=1,
-                  device=None, threads=0, mask=False, _lib=None):
-    """Records in HBM -> an archive (bytes), equal to what Encoder writes when the same records are pushed one by one.
+                  device=None, threads=0, mask=False, device_lz=False, _lib=None):
+    """Records in HBM -> an archive (bytes), equal to what Encoder writes when the same records are pushed one by one
+    (`device_lz=True` at compression_level 0 or >= 3: equal to Encoder(device=, device_lz=True)'s).
     `result` is what Decoder.decode_all_device() returns, or anything with its fields (d_sequence / n_bases, d_quality /
     n_quality, d_record_end / n_records, d_ids / n_ids_bytes, d_comments / n_comments_bytes) holding device addresses --
     a torch tensor's data_ptr() will do.  Only the enabled fields are read.  `mask=True`: the letters may be lower case, as
@@ -131,6 +136,7 @@ def encode_device(result, *, sequence_type="dna", id=False, comment=False, seque
     lib.c.nafgpu_encoder_opts_default(SEQUENCE_TYPES.index(sequence_type), byref(opts))
     opts.id, opts.comment, opts.sequence, opts.quality = map(int, (id, comment, sequence, quality))
     opts.compression_level, opts.threads, opts.mask = int(compression_level), int(threads), int(bool(mask))
+    opts.device_lz = int(bool(device_lz))
     src = _ffi.EncodeSource()
     src.n_records, src.d_record_end = int(result.n_records), result.d_record_end
     if id:
@@ -242,7 +248,7 @@ def parse_text(data, n=None, *, format=None, device=None, _lib=None):
 
 
 def encode_text(data, *, sequence_type="dna", id=True, comment=True, sequence=True, quality=None, mask=False, compression_level=1,
-                keep_line_length=True, format=None, device=None, threads=0, _lib=None):
+                keep_line_length=True, format=None, device=None, threads=0, device_lz=False, _lib=None):
     """FASTA / FASTQ text (bytes-like) -> an archive (bytes): parse_text and encode_device in one call, what `ennaf` does.
     `quality=None`: written if the text is FASTQ.  `keep_line_length=False`: the header says 60, and the archive is byte
     for byte what Encoder writes for the same records."""
@@ -260,6 +266,7 @@ def encode_text(data, *, sequence_type="dna", id=True, comment=True, sequence=Tr
     lib.c.nafgpu_encoder_opts_default(SEQUENCE_TYPES.index(sequence_type), byref(opts))
     opts.id, opts.comment, opts.sequence, opts.quality = map(int, (id, comment, sequence, quality))
     opts.compression_level, opts.threads, opts.mask = int(compression_level), int(threads), int(bool(mask))
+    opts.device_lz = int(bool(device_lz))
     p, n_out, err = c_void_p(), c_uint64(), _ffi.Error()
     rc = lib.c.nafgpu_encode_text(ptr, n, byref(popts), byref(opts), int(bool(keep_line_length)), -1 if device is None else int(device),
                                   byref(p), byref(n_out), byref(err))
