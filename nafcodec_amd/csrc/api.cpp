@@ -11,7 +11,6 @@
 #include <cstring>
 #include <future>
 #include <memory>
-#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
@@ -34,56 +33,6 @@ namespace {
 // consumed front to back, so one sliding window replaces the reference's per-record Strings.
 // The section may be resident whole, or a tile at a time (SectionJob::tiled_output): the window then
 // asks for the next tile whenever it runs off the end of the one in HBM -- positions only move forward.
-// Pinned memory outlives decoders: hipHostMalloc + hipHostFree of the window were 1.5 of the 5 ms a 5-Mbase archive takes open to
-// close (a caller that walks a directory of genomes pays them per file).  A closed decoder's windows go to a small per-process
-// pool -- at most kPinnedPoolKeep buffers -- and the next decoder takes the smallest one that is large enough.
-class PinnedPool {
-public:
-    static PinnedPool &get() {
-        static PinnedPool p;
-        return p;
-    }
-    uint8_t *take(uint64_t want, uint64_t *cap) {
-        std::lock_guard<std::mutex> g(mu_);
-        int best = -1;
-        for (int i = 0; i < n_; i++)
-            if (cap_[i] >= want && (best < 0 || cap_[i] < cap_[best])) best = i;
-        if (best < 0) return nullptr;
-        uint8_t *p = buf_[best];
-        *cap = cap_[best];
-        buf_[best] = buf_[n_ - 1];
-        cap_[best] = cap_[n_ - 1];
-        n_--;
-        return p;
-    }
-    void give(uint8_t *p, uint64_t cap) {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            if (n_ < kPinnedPoolKeep) {
-                buf_[n_] = p;
-                cap_[n_] = cap;
-                n_++;
-                return;
-            }
-            int small = 0;                                 // full: the smallest buffer makes room for a larger one
-            for (int i = 1; i < n_; i++)
-                if (cap_[i] < cap_[small]) small = i;
-            if (cap_[small] < cap) {
-                std::swap(buf_[small], p);
-                std::swap(cap_[small], cap);
-            }
-        }
-        (void)hipHostFree(p);
-    }
-
-private:
-    static constexpr int kPinnedPoolKeep = 4;
-    std::mutex mu_;
-    uint8_t *buf_[kPinnedPoolKeep] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t cap_[kPinnedPoolKeep] = {0, 0, 0, 0};
-    int n_ = 0;
-};
-
 // The bytes of one section the iterator hands out, on the host: a window of pinned memory that moves forward over the
 // section (the reference's BufReader over its zstd stream, mod.rs:223).  While the caller works through one window the next
 // one is already on its way into a second buffer (`ahead`): the link is then busy all the time, where waiting for each window
@@ -92,8 +41,8 @@ class HostWindow {
 public:
     ~HostWindow() {
         settle();
-        if (buf_) PinnedPool::get().give(buf_, cap_);
-        if (nbuf_) PinnedPool::get().give(nbuf_, ncap_);
+        if (buf_) PinnedPool::instance().give(buf_, cap_);
+        if (nbuf_) PinnedPool::instance().give(nbuf_, ncap_);
     }
     void bind(ArchiveJob *job, int section, uint64_t mult, uint64_t total, uint64_t window) {
         settle();
@@ -137,13 +86,13 @@ public:
         const uint64_t room = total_ > window_ ? std::max(want, window_ + kHead) : want;
         if (room > cap_) {
             uint64_t cap = room;
-            void *p = PinnedPool::get().take(room, &cap);
+            void *p = PinnedPool::instance().take(room, &cap);
             if (!p && hipHostMalloc(&p, room) != hipSuccess) {
                 *f = Failure::make(NAFGPU_E_DEVICE, "cannot allocate the pinned read-back window");
                 return nullptr;
             }
             if (keep) std::memcpy(p, base_ + (start - lo_), keep);
-            if (buf_) PinnedPool::get().give(buf_, cap_);
+            if (buf_) PinnedPool::instance().give(buf_, cap_);
             buf_ = static_cast<uint8_t *>(p);
             cap_ = cap;
         } else if (keep) {
@@ -220,9 +169,9 @@ private:
         if (n < std::min<uint64_t>(uint64_t(1) << 20, window_)) return;   // (the last bytes of a tile: the plain way)
         if (kHead + n > ncap_) {
             uint64_t cap = kHead + window_;
-            void *p = PinnedPool::get().take(cap, &cap);
+            void *p = PinnedPool::instance().take(cap, &cap);
             if (!p && hipHostMalloc(&p, kHead + window_) != hipSuccess) return;
-            if (nbuf_) PinnedPool::get().give(nbuf_, ncap_);
+            if (nbuf_) PinnedPool::instance().give(nbuf_, ncap_);
             nbuf_ = static_cast<uint8_t *>(p);
             ncap_ = cap;
         }

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <string>
 
@@ -37,6 +38,11 @@ struct Failure {                   // maps 1:1 onto nafgpu_error
     }
     void to_c(nafgpu_error *e) const;
 };
+inline int fail_c(nafgpu_error *err, const Failure &f) {   // the last line of a C-ABI entry point: *err filled, the status returned
+    if (err) std::memset(err, 0, sizeof *err);
+    f.to_c(err);
+    return f.status;
+}
 
 // what std::str::from_utf8 accepts
 bool utf8_valid(const uint8_t *p, uint64_t n);

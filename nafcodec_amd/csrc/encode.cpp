@@ -16,12 +16,11 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
 
-#include "engine.h"
+#include "device.h"
 #include "kernels.h"
 #include "plan.h"
 
@@ -29,10 +28,6 @@ namespace nafgpu {
 namespace enc {
 
 namespace {
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 thread_local EncTimes g_last_times;
 
@@ -326,12 +321,6 @@ Failure compress_section_device(const uint8_t *src, size_t n, bool src_on_device
 }
 
 namespace {
-
-int fail_c(nafgpu_error *err, const Failure &f) {
-    if (err) std::memset(err, 0, sizeof *err);
-    f.to_c(err);
-    return f.status;
-}
 
 Failure encode_device(const nafgpu_encode_source *src, const nafgpu_encoder_opts *opts, int device, uint64_t line_length, std::vector<uint8_t> &o) {
     if (opts->sequence_type > 3) return Failure::make(NAFGPU_E_INVALID_ARG, "invalid encoder options");

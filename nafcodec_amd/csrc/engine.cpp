@@ -4,24 +4,14 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include <atomic>
 #include <algorithm>
 #include <vector>
 #include <thread>
-#include <map>
-#include <mutex>
-#include <chrono>
 #include <cstring>
 
 namespace nafgpu {
 
-static std::atomic<bool> g_test_hooks{false};
-void set_test_hooks(bool on) { g_test_hooks.store(on); }
-const char *hook_env(const char *name) { return g_test_hooks.load() ? std::getenv(name) : nullptr; }
-
 namespace {
-inline bool hip_ok(hipError_t e) { return e == hipSuccess; }
-
 Failure dev_fail(const char *what, hipError_t e) {
     return Failure::make(NAFGPU_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
@@ -39,349 +29,7 @@ const char *status_text(uint32_t code) {
     default: return "zstd: device decoder reported an error";
     }
 }
-
-double now_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
 }  // namespace
-
-// ------------------------------------------------------------------ DevBuf
-bool DevBuf::alloc_items(uint64_t count, uint64_t item_bytes, uint64_t extra_bytes) {
-    // sizes derived from untrusted header fields: refuse anything that does not fit 63 bits instead of wrapping
-    if (item_bytes && count > ((1ull << 62) - extra_bytes) / item_bytes) return false;
-    return alloc(static_cast<size_t>(count * item_bytes + extra_bytes));
-}
-
-#ifndef NAFGPU_EMU
-namespace {
-// Large buffers come from the virtual-memory API: an address range backed by hipMemCreate chunks of up to 1 GiB.  Why: memory
-// from one large hipMalloc writes at 4.9-6.7 TB/s depending on the allocation (the same virtual address after a hipFree can
-// land on either side; tools/frontbench4.hip, profiles/r03_frontbench4.log -- a plain streaming fill shows it as well as
-// K1's 610 k write fronts), which is what made K1 take 10.7-11.9 ms on the same archive.  Chunked backing gave 6.7 TB/s in
-// nine allocations out of nine, whatever the chunk size (2 MiB, 64 MiB, 1 GiB).
-constexpr size_t kVmmMinBytes = size_t(32) << 20, kVmmChunk = size_t(1) << 30;
-constexpr int kSmallDevices = 16;                          // devices the process-wide pools below know of
-
-bool vmm_usable(int dev, size_t *gran) {
-    int ok = 0;
-    if (!hip_ok(hipDeviceGetAttribute(&ok, hipDeviceAttributeVirtualMemoryManagementSupported, dev)) || !ok) return false;
-    hipMemAllocationProp prop = {};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = dev;
-    return hip_ok(hipMemGetAllocationGranularity(gran, &prop, hipMemAllocationGranularityRecommended)) && *gran &&
-           kVmmChunk % *gran == 0;
-}
-}  // namespace
-
-// Mapped ranges outlive the buffers they were.  Unmapping a range and mapping memory at the same addresses a moment later is
-// (a) slow -- the address ranges and chunks of a 50 GB decoder take 10 ms in one process and 0.3-0.8 s in the next -- and
-// (b) NOT SAFE on this stack: a decoder that went from tiles to the whole output (its 2 GiB tile buffer unmapped and freed,
-// buffers of 4.4 GB and 1.1 GB reserved and mapped in the same call, the smaller one at the addresses just freed) found
-// about every other 4 KiB page of its freshly uploaded source bytes holding something else -- zeros where the chunks were
-// new, old bytes where they were reused (NAFGPU_DEBUG_VERIFY_UPLOAD; plain hipMalloc: fine; unmapping chunk by chunk and
-// keeping the chunks for reuse: no better).  Translations of the old mapping seem to outlive it.  So a released range stays
-// as it is -- reserved, mapped, its chunks in place -- and waits here for the next buffer of its size (sizes are multiples of
-// kVmmTail, so that they meet their like again; a range up to an eighth larger than asked for is taken too).  When a creation
-// fails for want of memory the idle ranges are unmapped and their chunks released, but their ADDRESSES are never given back:
-// no later mapping can land where an old one was.
-namespace {
-constexpr size_t kVmmTail = size_t(64) << 20;
-struct IdleRange {
-    void *va;
-    size_t total, chunk;
-    std::vector<hipMemGenericAllocationHandle_t> chunks;
-};
-struct RangePool {
-    std::mutex mu;
-    std::vector<IdleRange> idle[kSmallDevices];
-};
-RangePool &range_pool() {
-    static RangePool *p = new RangePool;
-    return *p;
-}
-bool range_take(int dev, size_t total, size_t chunk, IdleRange *out) {
-    RangePool &rp = range_pool();
-    std::lock_guard<std::mutex> lock(rp.mu);
-    auto &v = rp.idle[dev];
-    size_t best = v.size();
-    for (size_t i = 0; i < v.size(); i++)
-        if (v[i].chunk == chunk && v[i].total >= total && v[i].total - total <= total / 8 && (best == v.size() || v[i].total < v[best].total)) best = i;
-    if (best == v.size()) return false;
-    *out = std::move(v[best]);
-    v.erase(v.begin() + static_cast<std::ptrdiff_t>(best));
-    return true;
-}
-void range_drop(IdleRange &r) {                            // memory back to the driver, the addresses stay reserved
-    size_t k = 0;
-    for (size_t off = 0; off < r.total; off += r.chunk, k++) {
-        (void)hipMemUnmap(static_cast<char *>(r.va) + off, std::min(r.chunk, r.total - off));
-        if (k < r.chunks.size()) (void)hipMemRelease(r.chunks[k]);
-    }
-}
-// idle ranges kept per device at most (the oldest go first).  Not more: a process that holds -- or has just given back -- a hundred
-// gigabytes makes the NEXT process's first allocations take 0.5 s longer (bench.py's iterator legs run in children)
-constexpr size_t kVmmKeepBytes = size_t(16) << 30;
-void range_give(int dev, IdleRange &&r) {
-    RangePool &rp = range_pool();
-    std::lock_guard<std::mutex> lock(rp.mu);
-    auto &v = rp.idle[dev];
-    v.push_back(std::move(r));
-    size_t held = 0;
-    for (const IdleRange &e : v) held += e.total;
-    while (held > kVmmKeepBytes && v.size() > 1) {
-        held -= v.front().total;
-        range_drop(v.front());
-        v.erase(v.begin());
-    }
-}
-void range_trim(int dev) {                                 // the memory of everything idle goes back to the driver (not the addresses)
-    RangePool &rp = range_pool();
-    std::lock_guard<std::mutex> lock(rp.mu);
-    for (IdleRange &r : rp.idle[dev]) range_drop(r);
-    rp.idle[dev].clear();
-}
-}  // namespace
-
-bool DevBuf::alloc_mapped(size_t bytes) {
-    int dev = 0;
-    size_t gran = 0;
-    if (!hip_ok(hipGetDevice(&dev)) || dev < 0 || dev >= kSmallDevices || !vmm_usable(dev, &gran)) return false;
-    size_t chunk = kVmmChunk;
-    if (const char *ce = hook_env("NAFGPU_VMM_CHUNK_MIB")) {        // (experiments: tools/placement_probe.sh)
-        const size_t want = static_cast<size_t>(std::strtoull(ce, nullptr, 10)) << 20;
-        if (want >= gran && want % gran == 0) chunk = want;
-    }
-    const size_t tail_unit = kVmmTail % gran == 0 && chunk % kVmmTail == 0 ? kVmmTail : gran;
-    const size_t total = (bytes + tail_unit - 1) / tail_unit * tail_unit;
-    {
-        IdleRange r;
-        if (!hook_env("NAFGPU_VMM_NO_POOL") && range_take(dev, total, chunk, &r)) {
-            ptr_ = r.va;
-            size_ = bytes;
-            reserved_ = r.total;
-            chunk_bytes_ = r.chunk;
-            chunks_ = std::move(r.chunks);
-            return true;
-        }
-    }
-    void *va = nullptr;
-    if (!hip_ok(hipMemAddressReserve(&va, total, gran, nullptr, 0)) || !va) return false;
-    hipMemAllocationProp prop = {};
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = dev;
-    size_t mapped = 0;
-    bool ok = true;
-    for (size_t off = 0; off < total && ok; off += chunk) {
-        const size_t n = total - off < chunk ? total - off : chunk;
-        hipMemGenericAllocationHandle_t h;
-        if (!hip_ok(hipMemCreate(&h, n, &prop, 0))) {
-            (void)hipGetLastError();
-            range_trim(dev);                               // (what waits for a buffer of another size gives its memory back first)
-            if (!hip_ok(hipMemCreate(&h, n, &prop, 0))) { ok = false; break; }
-        }
-        if (!hip_ok(hipMemMap(static_cast<char *>(va) + off, n, 0, h, 0))) {
-            (void)hipMemRelease(h);
-            ok = false;
-            break;
-        }
-        chunks_.push_back(h);
-        mapped = off + n;
-    }
-    if (ok) {
-        hipMemAccessDesc acc = {};
-        acc.location = prop.location;
-        acc.flags = hipMemAccessFlagsProtReadWrite;
-        ok = hip_ok(hipMemSetAccess(va, total, &acc, 1));
-    }
-    if (!ok) {                                   // e.g. out of device memory: undo, the caller reports the failure of hipMalloc
-        for (size_t off = 0; off < mapped; off += chunk) (void)hipMemUnmap(static_cast<char *>(va) + off, std::min(chunk, mapped - off));
-        for (auto h : chunks_) (void)hipMemRelease(h);
-        chunks_.clear();
-        (void)hipMemAddressFree(va, total);
-        (void)hipGetLastError();
-        return false;
-    }
-    ptr_ = va;
-    size_ = bytes;
-    reserved_ = total;
-    chunk_bytes_ = chunk;
-    return true;
-}
-#endif
-
-#if !defined(NAFGPU_EMU) || defined(NAFGPU_EMU_CACHE)   // (NAFGPU_EMU_CACHE: a harness build WITH the cache, to chase what depends on it)
-#define NAFGPU_SMALL_CACHE 1
-#endif
-#ifdef NAFGPU_SMALL_CACHE
-// Small device buffers outlive their decoders.  Opening, decoding and closing one of the reference's fixtures makes a hundred
-// hipMalloc calls and as many hipFree calls, each of which waits for the device (rocprofv3 --hip-trace, tools/small_api_trace.sh:
-// 0.75 ms of a 3.6 ms cycle): buffers of up to 256 KiB come in power-of-two size classes, and one whose OWNER goes away (the
-// destructor: by then the owner's streams are drained, ~ArchiveJob) is kept for the next decoder on the same device -- up to
-// 64 MiB of them.  A buffer given up while its owner lives on (alloc() growing it) is freed as before: hipFree's wait is what
-// makes that safe.  Never torn down (the runtime may be gone before a static destructor runs).  The CPU harness does without:
-// rounded-up sizes would hide small overruns from the sanitizer.
-namespace {
-constexpr size_t kSmallMax = size_t(256) << 10, kSmallMin = 256, kSmallKeepBytes = size_t(64) << 20;
-constexpr int kSmallClasses = 11;                          // 256 B .. 256 KiB
-struct SmallCache {
-    std::mutex mu;
-    std::vector<void *> idle[kSmallDevices][kSmallClasses];
-    size_t bytes = 0;
-};
-SmallCache &small_cache() {
-    static SmallCache *c = new SmallCache;
-    return *c;
-}
-int small_class(size_t bytes) {
-    int c = 0;
-    while ((kSmallMin << c) < bytes) c++;
-    return c;
-}
-}  // namespace
-#endif
-
-void DevBuf::view(void *p, size_t bytes) {
-    release();
-    ptr_ = p;
-    size_ = bytes;
-    view_ = true;
-}
-
-bool DevBuf::alloc(size_t bytes) {
-    if (ptr_ && !view_ && bytes <= size_) return true;
-    release();
-    // (nafgpu_test_hooks + NAFGPU_ALLOC_PLAIN=1: everything from hipMalloc, for A/B runs -- tools/placement_probe.sh; any value:
-    //  no small-buffer cache)
-    const char *plain = hook_env("NAFGPU_ALLOC_PLAIN");
-#ifndef NAFGPU_EMU
-    if (bytes >= kVmmMinBytes && !(plain && plain[0] == '1') && alloc_mapped(bytes)) return true;
-#endif
-#ifdef NAFGPU_SMALL_CACHE
-    int dev = -1;
-    if (bytes <= kSmallMax && !plain && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kSmallDevices) {
-        const int c = small_class(bytes);
-        void *p = nullptr;
-        {
-            SmallCache &sc = small_cache();
-            std::lock_guard<std::mutex> lock(sc.mu);
-            std::vector<void *> &v = sc.idle[dev][c];
-            if (!v.empty()) {
-                p = v.back();
-                v.pop_back();
-                sc.bytes -= kSmallMin << c;
-            }
-        }
-        if (!p && !hip_ok(hipMalloc(&p, kSmallMin << c))) {
-            (void)hipGetLastError();
-            range_trim(dev);                               // (idle ranges give their memory back before anything fails for want of it)
-            if (!hip_ok(hipMalloc(&p, kSmallMin << c))) return false;
-        }
-        ptr_ = p;
-        size_ = kSmallMin << c;
-        cache_dev_ = dev;
-        return true;
-    }
-#endif
-    void *p = nullptr;
-    if (!hip_ok(hipMalloc(&p, bytes ? bytes : 16))) {
-#ifndef NAFGPU_EMU
-        (void)hipGetLastError();
-        int d = 0;
-        if (!hip_ok(hipGetDevice(&d)) || d < 0 || d >= kSmallDevices) return false;
-        range_trim(d);
-        if (!hip_ok(hipMalloc(&p, bytes ? bytes : 16))) return false;
-#else
-        return false;
-#endif
-    }
-    ptr_ = p;
-    size_ = bytes ? bytes : 16;
-    return true;
-}
-
-bool DevBuf::upload(const void *host, size_t bytes, hipStream_t stream) {
-    if (!alloc(bytes)) return false;
-    if (bytes == 0) return true;
-    return hip_ok(hipMemcpyAsync(ptr_, host, bytes, hipMemcpyHostToDevice, stream));
-}
-
-void DevBuf::release(bool dying) {
-    if (view_) {
-        ptr_ = nullptr;
-        size_ = 0;
-        view_ = false;
-        return;
-    }
-#ifdef NAFGPU_SMALL_CACHE
-    if (ptr_ && cache_dev_ >= 0) {
-        if (dying) {
-            SmallCache &sc = small_cache();
-            std::lock_guard<std::mutex> lock(sc.mu);
-            if (sc.bytes + size_ <= kSmallKeepBytes) {
-                sc.idle[cache_dev_][small_class(size_)].push_back(ptr_);
-                sc.bytes += size_;
-                ptr_ = nullptr;
-            }
-        }
-        cache_dev_ = -1;
-        if (!ptr_) {
-            size_ = 0;
-            return;
-        }
-    }
-#endif
-#ifndef NAFGPU_EMU
-    if (ptr_ && reserved_) {
-        // (range_pool above: why the range is kept as it is rather than unmapped)
-        int dev = 0;
-        if (hip_ok(hipGetDevice(&dev)) && dev >= 0 && dev < kSmallDevices && !hook_env("NAFGPU_VMM_NO_POOL")) {
-            if (!dying) (void)hipDeviceSynchronize();      // (a living owner: whatever it still has in flight is done before another takes the range)
-            IdleRange r{ptr_, reserved_, chunk_bytes_ ? chunk_bytes_ : reserved_, std::move(chunks_)};
-            range_give(dev, std::move(r));
-        } else {                                           // chunk by chunk, as they were mapped
-            if (hook_env("NAFGPU_VMM_SYNC_UNMAP")) (void)hipDeviceSynchronize();   // (experiment: is anything still in flight on the range?)
-            const size_t step = chunk_bytes_ ? chunk_bytes_ : reserved_;
-            size_t k = 0;
-            for (size_t off = 0; off < reserved_; off += step, k++) {
-                (void)hipMemUnmap(static_cast<char *>(ptr_) + off, std::min(step, reserved_ - off));
-                if (k < chunks_.size()) (void)hipMemRelease(chunks_[k]);
-            }
-            (void)hipMemAddressFree(ptr_, reserved_);
-        }
-        chunks_.clear();
-        ptr_ = nullptr;
-    }
-#endif
-    if (ptr_) (void)hipFree(ptr_);
-    ptr_ = nullptr;
-    size_ = reserved_ = 0;
-}
-
-void trim_device_memory(int device) {
-#ifndef NAFGPU_EMU
-    if (device < 0 || device >= kSmallDevices) return;
-    (void)hipDeviceSynchronize();
-    range_trim(device);
-    std::vector<void *> gone;
-    {
-        SmallCache &sc = small_cache();
-        std::lock_guard<std::mutex> lock(sc.mu);
-        for (int c = 0; c < kSmallClasses; c++) {
-            for (void *p : sc.idle[device][c]) {
-                gone.push_back(p);
-                sc.bytes -= kSmallMin << c;
-            }
-            sc.idle[device][c].clear();
-        }
-    }
-    for (void *p : gone) (void)hipFree(p);
-#else
-    (void)device;
-#endif
-}
 
 // ------------------------------------------------------------------ StageTimer
 StageTimer::~StageTimer() {
@@ -443,88 +91,6 @@ StageTimes StageTimer::collect() {
 }
 
 // ------------------------------------------------------------------ SectionJob
-// Host -> device for the compressed bytes of a section.  One hipMemcpyAsync out of ordinary or mapped memory moves at PCIe rate in
-// one process and at a quarter of it in the next -- the runtime's copy engines again (see k_copy_out: 10 GB in 0.2 s or in 1.2 s,
-// tools/iter_regime_probe.py) -- so large uploads take the same road as the read-back: kStageThreads host threads copy their
-// chunks of the source into pinned buffers (two of 16 MiB each, so the memcpy of one overlaps the transfer of the other; the
-// page faults of a file mapping spread over the threads as well), and the GPU fetches every chunk itself (k_copy_out with
-// the pinned buffer as its source).  Returns when every byte is on the device.
-#ifndef NAFGPU_EMU
-namespace {
-constexpr size_t kStageChunk = size_t(16) << 20;
-constexpr unsigned kStageThreads = 8;
-constexpr size_t kStageMin = size_t(256) << 20;            // smaller uploads: one plain copy
-struct StageSlot {
-    uint8_t *buf[2] = {nullptr, nullptr};
-    hipStream_t stream = nullptr;
-    hipEvent_t done[2] = {nullptr, nullptr};
-};
-std::mutex g_stage_mu;                                     // one staged upload at a time per process (the buffers are shared)
-StageSlot g_stage[kStageThreads];
-bool g_stage_ready = false, g_stage_failed = false;
-bool stage_init() {
-    if (g_stage_ready) return true;
-    if (g_stage_failed) return false;
-    for (unsigned t = 0; t < kStageThreads; t++) {
-        StageSlot &sl = g_stage[t];
-        bool ok = hipStreamCreate(&sl.stream) == hipSuccess;
-        for (int k = 0; k < 2 && ok; k++)
-            ok = hipHostMalloc(reinterpret_cast<void **>(&sl.buf[k]), kStageChunk) == hipSuccess &&
-                 hipEventCreateWithFlags(&sl.done[k], hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-            g_stage_failed = true;                         // (what was allocated stays: a plain copy serves from here on)
-            return false;
-        }
-    }
-    g_stage_ready = true;
-    return true;
-}
-}  // namespace
-#endif
-
-bool upload_staged(uint8_t *d_dst, const uint8_t *src, size_t n, hipStream_t stream, size_t stage_min) {
-#ifndef NAFGPU_EMU
-    if (n >= (stage_min ? stage_min : kStageMin) && !hook_env("NAFGPU_NO_STAGING")) {
-        std::lock_guard<std::mutex> guard(g_stage_mu);
-        if (stage_init() && hipStreamSynchronize(stream) == hipSuccess) {   // (what was enqueued in front -- the pad memsets -- is done)
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            const size_t n_chunks = (n + kStageChunk - 1) / kStageChunk;
-            std::atomic<bool> failed{false};
-            const bool sdma = hook_env("NAFGPU_STAGE_SDMA") != nullptr;   // (experiment: the copy engines fetch the chunks, not a kernel)
-            auto worker = [&](unsigned t) {
-                (void)hipSetDevice(dev);
-                StageSlot &sl = g_stage[t];
-                unsigned k = 0;
-                for (size_t c = t; c < n_chunks && !failed.load(); c += kStageThreads, k ^= 1u) {
-                    const size_t off = c * kStageChunk, len = std::min(kStageChunk, n - off);
-                    if (hipEventSynchronize(sl.done[k]) != hipSuccess) failed = true;   // (the kernel that last read this buffer)
-                    std::memcpy(sl.buf[k], src + off, len);
-                    if (sdma) {
-                        if (hipMemcpyAsync(d_dst + off, sl.buf[k], len, hipMemcpyHostToDevice, sl.stream) != hipSuccess) failed = true;
-                    } else {
-                        launch_copy_out(sl.stream, d_dst + off, sl.buf[k], len);
-                    }
-                    if (hipGetLastError() != hipSuccess || hipEventRecord(sl.done[k], sl.stream) != hipSuccess) failed = true;
-                }
-                if (hipStreamSynchronize(sl.stream) != hipSuccess) failed = true;
-            };
-            std::vector<std::thread> pool;
-            unsigned started = 1;
-            try {
-                for (; started < kStageThreads; started++) pool.emplace_back(worker, started);
-            } catch (...) {                                // no more threads to be had: their chunks are done here
-            }
-            worker(0);
-            for (unsigned t = started; t < kStageThreads; t++) worker(t);
-            for (std::thread &th : pool) th.join();
-            return !failed.load();
-        }
-    }
-#endif
-    return hipMemcpyAsync(d_dst, src, n, hipMemcpyHostToDevice, stream) == hipSuccess;
-}
-
 // tiles whose compressed bytes are fewer travel with load_tile itself (NAFGPU_SRC_PREFETCH_MIN: tests lower it)
 static size_t src_prefetch_min() {
     if (const char *e = hook_env("NAFGPU_SRC_PREFETCH_MIN")) return static_cast<size_t>(std::strtoull(e, nullptr, 10));
@@ -1499,63 +1065,13 @@ Failure SectionJob::check(hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------ ArchiveJob
-namespace {
-// Streams outlive decoders.  hipStreamCreate takes 2.7 ms and hipStreamDestroy 2.4 ms on this stack (rocprofv3 --hip-trace of
-// tools/small_probe.py: 80 % of the 14-18 ms that opening, decoding and closing ONE of the reference's fixtures took, whatever
-// its size -- a decoder owns three streams), so a closed decoder hands its streams to the next one on the same device.  A
-// stream is idle when it comes back (synchronised), a few per device are kept, and the pool is never torn down: at process
-// exit the runtime may be gone before a static destructor runs.
-class StreamPool {
-public:
-    static StreamPool &instance() {
-        static StreamPool *pool = new StreamPool;
-        return *pool;
-    }
-    hipStream_t get(int device) {                          // the current device is `device`
-        {
-            std::lock_guard<std::mutex> lock(mu_);
-            std::vector<hipStream_t> &v = idle_[device];
-            if (!v.empty()) {
-                hipStream_t s = v.back();
-                v.pop_back();
-                return s;
-            }
-        }
-        hipStream_t s = nullptr;
-        if (!hip_ok(hipStreamCreate(&s))) return nullptr;
-        return s;
-    }
-    void put(int device, hipStream_t s) {
-        if (!s) return;
-        (void)hipStreamSynchronize(s);
-        {
-            std::lock_guard<std::mutex> lock(mu_);
-            std::vector<hipStream_t> &v = idle_[device];
-            if (v.size() < kKeep) {
-                v.push_back(s);
-                return;
-            }
-        }
-        (void)hipStreamDestroy(s);
-    }
-
-private:
-    static constexpr size_t kKeep = 12;
-    std::mutex mu_;
-    std::map<int, std::vector<hipStream_t>> idle_;
-};
-}  // namespace
-
-hipStream_t pooled_stream_get(int device) { return StreamPool::instance().get(device); }
-void pooled_stream_put(int device, hipStream_t s) { StreamPool::instance().put(device, s); }
-
 ArchiveJob::~ArchiveJob() {
     if (stream_ || aux_stream_ || k2_stream_) (void)hipSetDevice(device_);
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_join_) (void)hipEventDestroy(ev_join_);
-    StreamPool::instance().put(device_, aux_stream_);
-    StreamPool::instance().put(device_, k2_stream_);
-    StreamPool::instance().put(device_, stream_);
+    pooled_stream_put(device_, aux_stream_);
+    pooled_stream_put(device_, k2_stream_);
+    pooled_stream_put(device_, stream_);
 }
 
 Failure ArchiveJob::init(int device) {
@@ -1572,10 +1088,10 @@ Failure ArchiveJob::init(int device) {
     if (!hip_ok(e)) return dev_fail("hipSetDevice", e);
     device_ = device;
     if (!stream_) {
-        stream_ = StreamPool::instance().get(device);
+        stream_ = pooled_stream_get(device);
         if (!stream_) return dev_fail("hipStreamCreate", hipGetLastError());
-        aux_stream_ = StreamPool::instance().get(device);   // optional: K1 then stays on one stream
-        k2_stream_ = StreamPool::instance().get(device);    // optional: K2 of a section beside the section before
+        aux_stream_ = pooled_stream_get(device);   // optional: K1 then stays on one stream
+        k2_stream_ = pooled_stream_get(device);    // optional: K2 of a section beside the section before
     }
     return Failure();
 }
@@ -1740,40 +1256,6 @@ Failure ArchiveJob::decode() {
     }
     return decode_back();
 }
-
-namespace {
-// Pinned host blocks for small read-backs (a copy into ordinary memory keeps its caller until it is done, 37 us apiece; into
-// pinned memory it is enqueued in 5): blocks of 16 KiB, handed back when done, never freed.
-constexpr size_t kPinnedBlock = size_t(16) << 10;
-class PinnedBlocks {
-public:
-    static PinnedBlocks &instance() {
-        static PinnedBlocks *p = new PinnedBlocks;
-        return *p;
-    }
-    uint8_t *take() {
-        {
-            std::lock_guard<std::mutex> lock(mu_);
-            if (!idle_.empty()) {
-                uint8_t *p = idle_.back();
-                idle_.pop_back();
-                return p;
-            }
-        }
-        void *p = nullptr;
-        return hipHostMalloc(&p, kPinnedBlock) == hipSuccess ? static_cast<uint8_t *>(p) : nullptr;
-    }
-    void give(uint8_t *p) {
-        if (!p) return;
-        std::lock_guard<std::mutex> lock(mu_);
-        idle_.push_back(p);
-    }
-
-private:
-    std::mutex mu_;
-    std::vector<uint8_t *> idle_;
-};
-}  // namespace
 
 Failure ArchiveJob::copy_small_to_host(const SmallCopy *copies, int count) {
     (void)hipSetDevice(device_);

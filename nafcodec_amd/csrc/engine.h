@@ -1,6 +1,6 @@
 // engine.h -- device-side orchestration: buffers in HBM, kernel sequence per section, timing.
 //
-// Data layout in HBM (hipMalloc'ed, from 32 MiB on address ranges backed by hipMemCreate chunks; 256-byte aligned, sized for a 288 GB device):
+// Data layout in HBM (DevBuf, device.h: hipMalloc'ed, from 32 MiB on address ranges backed by hipMemCreate chunks; 256-byte aligned, sized for a 288 GB device):
 //   archive   [256 B pad][archive bytes][64 B pad]      compressed input, uploaded once
 //   per zstd section:
 //     out       decoded bytes (packed 4-bit for DNA/RNA sequence, text otherwise)
@@ -21,38 +21,11 @@
 #include <vector>
 
 #include "container.h"
+#include "device.h"
 #include "kernels.h"
 #include "zplan.h"
 
 namespace nafgpu {
-
-class DevBuf {
-public:
-    DevBuf() = default;
-    ~DevBuf() { release(true); }
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    bool alloc(size_t bytes);                 // contents undefined
-    bool alloc_items(uint64_t count, uint64_t item_bytes, uint64_t extra_bytes = 0);   // count * item_bytes + extra_bytes, overflow-checked
-    bool upload(const void *host, size_t bytes, hipStream_t stream);   // alloc + async H2D
-    void release(bool dying = false);       // dying: the owner goes away (its streams are drained): a small buffer goes to the cache below
-    void view(void *p, size_t bytes);         // a piece of another buffer: not owned, release() only forgets it
-    template <class T>
-    T *as() const { return static_cast<T *>(ptr_); }
-    uint8_t *bytes() const { return static_cast<uint8_t *>(ptr_); }
-    size_t size() const { return size_; }
-
-private:
-    bool alloc_mapped(size_t bytes);          // an address range backed by hipMemCreate chunks (engine.cpp: why)
-    void *ptr_ = nullptr;
-    size_t size_ = 0, reserved_ = 0;          // reserved_ != 0: ptr_ is such a range
-    bool view_ = false;
-    int cache_dev_ = -1;                      // >= 0: ptr_ is a size-class buffer of that device's cache (engine.cpp: SmallCache)
-#ifndef NAFGPU_EMU
-    std::vector<hipMemGenericAllocationHandle_t> chunks_;
-    size_t chunk_bytes_ = 0;                  // every chunk but the last maps this many bytes
-#endif
-};
 
 struct StageTimes {          // milliseconds, summed over launches of the last run
     float huf = 0, seq_lz = 0, unpack = 0, other = 0, total = 0;
@@ -263,13 +236,6 @@ struct ArchiveOptions {
     uint64_t tile_blocks = 0;                   // > 0: sequence / quality sections are decoded in tiles of at most this many zstd blocks
     bool tiled_output = false;                  // ... whose output is held one tile at a time (iterator path; not for decode_all_device)
 };
-
-// a stream of the pool that closed decoders leave theirs in (engine.cpp: StreamPool); the current device is `device`.
-// put: the stream is synchronised and kept for the next taker
-hipStream_t pooled_stream_get(int device);
-void pooled_stream_put(int device, hipStream_t s);
-bool upload_staged(uint8_t *d_dst, const uint8_t *src, size_t n, hipStream_t stream, size_t stage_min = 0);
-void trim_device_memory(int device);             // engine.cpp: the idle mapped ranges and small buffers of `device` go back to the driver   // engine.cpp: large host -> device copies
 
 // A whole archive on one GPU: sections -> record table -> ASCII bases.
 class ArchiveJob {

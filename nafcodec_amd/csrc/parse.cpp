@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "encode.h"
-#include "engine.h"
+#include "device.h"
 
 using namespace nafgpu;
 using namespace nafgpu::parse;
@@ -35,12 +35,6 @@ struct nafgpu_parsed {
 namespace {
 
 Failure device_failure(const char *what) { return Failure::make(NAFGPU_E_DEVICE, std::string("parse: ") + what); }
-
-int fail_c(nafgpu_error *err, const Failure &f) {
-    if (err) std::memset(err, 0, sizeof *err);
-    f.to_c(err);
-    return f.status;
-}
 
 struct Events {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -152,7 +152,7 @@ def test_synthetic_archive(lib, n_bases, mask, iupac):
 
 
 def test_large_buffers_from_plain_hipmalloc_and_from_mapped_chunks(lib, monkeypatch):
-    """DevBuf takes buffers of 32 MiB and more from the virtual-memory API (an address range backed by hipMemCreate chunks, engine.cpp);
+    """DevBuf takes buffers of 32 MiB and more from the virtual-memory API (an address range backed by hipMemCreate chunks, device.cpp);
     NAFGPU_ALLOC_PLAIN=1 keeps everything on hipMalloc, NAFGPU_VMM_CHUNK_MIB changes the chunk size: the same archive decodes to
     the same checksums on all of them, twice per decoder (the second call reuses the buffers), and the buffers go away with the
     decoder (a loop of decoders would run out of device memory otherwise)."""
@@ -487,7 +487,7 @@ def test_encoder_output_decodes_on_the_gpu(lib):
 @pytest.mark.gpu
 def test_decoders_in_several_threads_at_once(lib):
     """Decoders are independent objects: four threads each open, read and close the reference's fixtures and a few generated
-    archives over and over (ctypes releases the GIL inside every call), sharing the library's process-wide pools -- streams,
+    archives over and over (ctypes releases the GIL inside every call), sharing the library's pools -- streams,
     pinned windows, small device buffers, the staging threads of large uploads.  Every run must give the oracle's records."""
     import threading
     todo = [(n, golden_bytes(n + ".naf"), {}) for n in ("NZ_AAEN01000029", "phix", "LuxC", "masked")]
@@ -515,7 +515,7 @@ def test_decoders_in_several_threads_at_once(lib):
 @pytest.mark.gpu
 def test_kept_device_memory_is_given_back_on_request(lib):
     """Closed decoders leave their large mapped ranges and small buffers to the next decoder of the process
-    (engine.cpp: range_pool, SmallCache); nafgpu_trim_device_memory gives them back to the driver, and a decoder after that
+    (device.cpp: DeviceState, its idle ranges and small buffers); nafgpu_trim_device_memory gives them back to the driver, and a decoder after that
     works as one before it."""
     hip = ctypes.CDLL("libamdhip64.so")                     # (the runtime the library itself is linked to: hipMemGetInfo)
 
@@ -543,3 +543,31 @@ def test_kept_device_memory_is_given_back_on_request(lib):
         once()
     finally:
         lib.c.nafgpu_synth_free(ctypes.byref(arc))
+
+
+@pytest.mark.gpu
+def test_staged_upload_on_every_device(lib):
+    """Uploads of 256 MiB and more go through the staging slots of the device they are bound for (device.cpp: upload_staged):
+    eight host threads, two pinned 16 MiB buffers each, the GPU fetching every chunk on the slot's stream.  256 MiB + 1 is the
+    smallest input that takes this road at its default threshold: all eight slots, both buffers of slot 0 (chunks 0, 8 and 16:
+    a buffer reused behind its event) and a last chunk of one byte.  The literal-only compressor is the cheapest consumer of
+    an upload; what it wrote must decode to the input.  Device 0 first, then device 1 in the same process: the order in which
+    slots made for the first device would serve a buffer of the second."""
+    n = (256 << 20) + 1
+    data = np.frombuffer(b"ACGT", dtype=np.uint8)[np.random.default_rng(2561).integers(0, 4, n, dtype=np.uint8)].tobytes()
+    want = lib.c.nafgpu_hash64_host(data, n)
+
+    def round_trip(dev):
+        out = lib.zstd_decompress(lib.zstd_compress(data, dev, False), n, dev)
+        assert len(out) == n, dev
+        assert lib.c.nafgpu_hash64_host(out, n) == want, dev
+
+    round_trip(0)
+    try:
+        lib.device_info(1)
+    except RuntimeError:
+        pytest.skip("one device here: the upload to a second device did not run (device 0's ran and matched)")
+    try:
+        round_trip(1)
+    finally:
+        lib.zstd_compress(b"ACGT" * 16, 0)                 # (the thread's current device is 0 again for the tests that follow)
