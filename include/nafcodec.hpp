@@ -58,6 +58,72 @@ private:
     nafgpu_header h_;
 };
 
+// (no counterpart in the reference) one region of a decoded archive for Decoder::select: the letters [start, end) of a
+// record, Region::npos = up to the record's end; reverse(): the reverse strand (nucleotide archives).  nafgpu.h has the rules.
+struct Region {
+    static constexpr uint64_t npos = NAFGPU_REGION_END;
+    explicit Region(uint64_t record, uint64_t start = 0, uint64_t end = npos) : r{record, start, end, 0, {0, 0, 0, 0, 0, 0, 0}} {}
+    Region slice(uint64_t start, uint64_t end) const {
+        Region out = *this;
+        out.r.start = start;
+        out.r.end = end;
+        return out;
+    }
+    Region reverse(bool on = true) const {
+        Region out = *this;
+        out.r.reverse_complement = on ? 1 : 0;
+        return out;
+    }
+    nafgpu_region r;
+};
+static_assert(sizeof(Region) == sizeof(nafgpu_region), "a vector of Region is an array of nafgpu_region");
+
+// What Decoder::select returns: records cut out of a decoded archive, in HBM; a copy that outlives the decoder.  Move-only.
+class Selection {
+public:
+    Selection(Selection &&o) noexcept : s_(std::exchange(o.s_, nullptr)), res_(o.res_) {}
+    Selection &operator=(Selection &&o) noexcept {
+        if (this != &o) {
+            nafgpu_selection_free(s_);
+            s_ = std::exchange(o.s_, nullptr);
+            res_ = o.res_;
+        }
+        return *this;
+    }
+    Selection(const Selection &) = delete;
+    ~Selection() { nafgpu_selection_free(s_); }
+
+    const nafgpu_encode_source &source() const { return res_.src; }   // device pointers: what encode_device takes
+    const nafgpu_select_result &result() const { return res_; }
+    uint64_t n_regions() const { return res_.n_regions; }
+    uint64_t n_records() const { return res_.src.n_records; }
+    uint64_t n_bases() const { return res_.src.n_bases; }
+    // FASTA (FASTQ when the selection has qualities) in lines of line_length letters (0: one line), formatted on the GPU
+    std::string to_text(uint64_t line_length = 60) {
+        nafgpu_text_result t;
+        check(nafgpu_selection_format(s_, line_length, &t), "nafgpu_selection_format", "the selection has no sequence field, so no text");
+        std::string out(static_cast<size_t>(t.n_text), '\0');
+        check(nafgpu_selection_copy_to_host(s_, t.d_text, t.n_text, out.data()), "nafgpu_selection_copy_to_host", "a null argument");
+        return out;
+    }
+    nafgpu_selection *raw() const { return s_; }
+
+private:
+    friend class Decoder;
+    Selection(nafgpu_selection *s, const nafgpu_select_result &r) : s_(s), res_(r) {}
+    // the calls on a selection return a status alone: the message says which call it was and what that status means there
+    static void check(int status, const char *call, const char *invalid_arg) {
+        if (status == NAFGPU_OK) return;
+        nafgpu_error e{};
+        e.status = status;
+        std::snprintf(e.message, sizeof e.message, "%s: %s", call,
+                      status == NAFGPU_E_INVALID_ARG ? invalid_arg : status == NAFGPU_E_DEVICE ? "the device failed (allocation, copy or kernel)" : "failed");
+        throw Error(e);
+    }
+    nafgpu_selection *s_ = nullptr;
+    nafgpu_select_result res_{};
+};
+
 class Decoder {   // mod.rs:285-461
 public:
     Decoder(Decoder &&o) noexcept
@@ -140,6 +206,29 @@ public:
             throw Error(e);
         }
         return out;
+    }
+    // (no counterpart in the reference) for every name the index of the first record with that id, looked up on the GPU
+    std::vector<std::optional<uint64_t>> find(const std::vector<std::string> &names) {
+        std::string blob;
+        for (const std::string &n : names) blob.append(n.c_str()).push_back('\0');
+        std::vector<uint64_t> at(names.size() + 1);
+        nafgpu_error e{};
+        if (nafgpu_find_records(d_, reinterpret_cast<const uint8_t *>(blob.data()), blob.size(), names.size(), at.data(), &e) != NAFGPU_OK) throw Error(e);
+        std::vector<std::optional<uint64_t>> out(names.size());
+        for (size_t k = 0; k < names.size(); k++)
+            if (at[k] != UINT64_MAX) out[k] = at[k];
+        return out;
+    }
+    // (no counterpart in the reference) regions -> records in HBM, region k the selection's record k; name_regions: ids
+    // become id:START-END (and /rc).  Throws Error (NAFGPU_E_INVALID_ARG, naming the first region the rules refuse).
+    Selection select(const std::vector<Region> &regions, bool name_regions = false) {
+        nafgpu_select_opts o{};
+        o.name_regions = name_regions ? 1 : 0;
+        nafgpu_selection *s = nullptr;
+        nafgpu_select_result r;
+        nafgpu_error e{};
+        if (nafgpu_select(d_, regions.empty() ? nullptr : &regions[0].r, regions.size(), &o, &s, &r, &e) != NAFGPU_OK) throw Error(e);
+        return Selection(s, r);
     }
     nafgpu_decoder *raw() const { return d_; }
 
@@ -289,6 +378,17 @@ inline std::string encode_device(const nafgpu_encode_source &src, const EncoderB
     std::string out(reinterpret_cast<const char *>(p), n);
     nafgpu_encode_free(p);
     return out;
+}
+
+// a selection -> an archive: the fields `fields` names (those the selection does not hold: nafgpu_encode_device refuses)
+inline std::string encode_device(const Selection &sel, const EncoderBuilder &fields, int device = -1) {
+    nafgpu_encode_source src = sel.source();
+    const nafgpu_encoder_opts &o = fields.options();
+    if (!o.id) src.d_ids = nullptr, src.n_ids_bytes = 0;
+    if (!o.comment) src.d_comments = nullptr, src.n_comments_bytes = 0;
+    if (!o.sequence) src.d_sequence = nullptr, src.n_bases = 0;
+    if (!o.quality) src.d_quality = nullptr, src.n_quality = 0;
+    return encode_device(src, fields, device);
 }
 
 // (no counterpart in the reference; what `ennaf` does) FASTA / FASTQ text -> an archive, parsed and encoded on the GPU:

@@ -447,6 +447,69 @@ void nafgpu_parse_free(nafgpu_parsed *parsed);
 int nafgpu_encode_text(const uint8_t *text, uint64_t n, const nafgpu_parse_opts *popts, const nafgpu_encoder_opts *opts,
                        int keep_line_length, int device, uint8_t **bytes, uint64_t *n_out, nafgpu_error *err);
 
+/* ---- records and regions of a decoded archive -> a new set of records in HBM (what a user of a decoded genome or read set does
+ * first: one chromosome, bases 1 000 000-1 050 000 of a contig, the reverse strand of a gene, a list of reads by name) ----
+ * The gather and the id lookup run in HIP kernels (select.hip); no decoded byte crosses to the host.  The reference has no
+ * counterpart.  Rules:
+ *   shape     nafgpu_select runs decode_all_device first if nothing is decoded yet.  Region k becomes output record k; regions
+ *             may come in any order, may repeat and may overlap.  Zero regions: an empty selection (all counts 0), no error.
+ *             The selection holds the fields the decoder was opened with; a field that was not decoded is a NULL pointer in
+ *             `src` (without opts.sequence: ids, comments and record ends only, n_bases 0).  It is a COPY: it stays valid
+ *             after nafgpu_close of the decoder, until nafgpu_selection_free.
+ *   sequence  the letters [start, end) of the record as they lie in d_sequence: soft-masked letters stay lower case.  With
+ *             reverse_complement the slice is reversed and every letter complemented, keeping its case: A<->T (A<->U in an
+ *             RNA archive), C<->G, R<->Y, K<->M, B<->V, D<->H; S, W, N and '-' map to themselves -- the format's 4-bit code
+ *             with its bits reversed (encoder/writer.rs:33-49); any other byte is copied unchanged.
+ *   quality   the same slice, reversed when the region is reverse-complemented.
+ *   names     the comment of the source record is copied, and its id; with opts->name_regions the id of EVERY region of the
+ *             call (whole records included) becomes id:START-END, START = start + 1 and END = the resolved end, in decimal
+ *             (`samtools faidx` coordinates), with "/rc" appended for a reverse-complemented region.  A source record without
+ *             an id or comment string (the archive may list fewer strings than records) gives an empty string.
+ *   refusals  NAFGPU_E_INVALID_ARG: record >= the number of records; start > the resolved end; an explicit end beyond the
+ *             record's length; reverse_complement on a protein or text archive -- the message names the LOWEST offending
+ *             region index (the check runs on the device, where the record lengths are); a shard, a tiled output (as
+ *             nafgpu_format_device); no Length section.  The tiled-output refusal cannot be reached through today's entry
+ *             points: nafgpu_select asks the engine for the whole output, as nafgpu_format_device does, so the refusal
+ *             guards the engine's state and not a caller's argument, and no test reaches it.  A record whose letters lie
+ *             beyond what was decoded: NAFGPU_E_IO / NAFGPU_IO_UNEXPECTED_EOF, as nafgpu_format_device gives.  On any error
+ *             nothing is produced. */
+#define NAFGPU_REGION_END UINT64_MAX
+typedef struct {
+    uint64_t record;             /* index among the records the decoder yields */
+    uint64_t start, end;         /* letters [start, end) of that record, 0-based; end = NAFGPU_REGION_END: the record's length */
+    uint8_t reverse_complement;  /* nucleotide archives only */
+    uint8_t reserved[7];
+} nafgpu_region;
+typedef struct { uint8_t name_regions; uint8_t reserved[7]; } nafgpu_select_opts;
+typedef struct nafgpu_selection nafgpu_selection;      /* owns its device buffers, like nafgpu_parsed */
+typedef struct {
+    nafgpu_encode_source src;    /* feed it to nafgpu_encode_device as it is */
+    const uint64_t *d_id_end, *d_comment_end;   /* as in nafgpu_device_result; n_regions entries each (NULL with its field) */
+    uint64_t n_regions;
+    float ms;                    /* the selection kernels, HIP events */
+} nafgpu_select_result;
+/* opts may be NULL (ids copied as they are).  An error is also kept for nafgpu_last_error. */
+int nafgpu_select(nafgpu_decoder *dec, const nafgpu_region *regions, uint64_t n_regions, const nafgpu_select_opts *opts,
+                  nafgpu_selection **out, nafgpu_select_result *res, nafgpu_error *err);
+/* record_out[j] = the lowest record index whose id equals name j byte for byte, or UINT64_MAX when there is none (that is
+ * NAFGPU_OK, not an error); equal ids in the archive resolve to the first.  Needs the ids decoded (opts.id), else
+ * NAFGPU_E_INVALID_ARG; `names` must hold exactly n_names NUL-terminated strings, concatenated, in n_bytes, else
+ * NAFGPU_E_INVALID_ARG.  An open-addressing table in HBM, keyed by a hash of the id bytes, built by one kernel and probed
+ * by another; every hit is verified byte by byte. */
+int nafgpu_find_records(nafgpu_decoder *dec, const uint8_t *names, uint64_t n_bytes, uint64_t n_names, uint64_t *record_out,
+                        nafgpu_error *err);
+/* The selection as text, by the rules at nafgpu_format_device (FASTQ when the selection has qualities; the name separator of
+ * the source archive's header), in lines of `line_length` letters (0: one line).  d_text is owned by the selection and
+ * stays valid until the next call or nafgpu_selection_free.
+ * The calls on a selection return a status alone, and each status has one meaning there: NAFGPU_E_INVALID_ARG is a NULL
+ * argument or, for nafgpu_selection_format, a selection without the sequence field; NAFGPU_E_DEVICE is an allocation, copy
+ * or kernel that failed. */
+int nafgpu_selection_format(nafgpu_selection *sel, uint64_t line_length, nafgpu_text_result *out);
+int nafgpu_selection_copy_to_host(nafgpu_selection *sel, const void *d_ptr, uint64_t n, void *dst);
+/* as nafgpu_hash64_device_at */
+int nafgpu_selection_hash64(nafgpu_selection *sel, const void *d_ptr, uint64_t n, uint64_t first_chunk, uint64_t *out);
+void nafgpu_selection_free(nafgpu_selection *sel);
+
 /* order-sensitive 64-bit checksum used for full-size parity checks: sum over the 8-byte words w_j of
  * mix64(w_j ^ (j + 1) * K) -- every word is mixed non-linearly with its position before it is added, so
  * byte errors cannot cancel -- see hash64.h */

@@ -3,13 +3,13 @@
 Python mirror of the reference's public surface for the decode path
 (nafcodec-py/nafcodec/lib.pyi:18-67 and __init__.py:3-9): `Decoder`, `Record`, `open`.
 All decoding happens on the GPU inside libnafgpu.so (include/nafgpu.h); there is no CPU path."""
-from .decoder import Decoder, Record, open  # noqa: F401
+from .decoder import Decoder, Record, Selection, open  # noqa: F401
 from .encoder import Encoder, encode_device, encode_text, parse_text, zstd_compress  # noqa: F401
 from ._ffi import NafError  # noqa: F401
 
 __version__ = "0.1.0"
 __all__ = ["Decoder", "Encoder", "Record", "open", "NafError", "trim_device_memory", "encode_device", "zstd_compress",
-           "parse_text", "encode_text"]
+           "parse_text", "encode_text", "Selection"]
 
 
 def trim_device_memory(device=-1):

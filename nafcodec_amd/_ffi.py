@@ -105,6 +105,24 @@ class ParseResult(Structure):
                 ("ms", c_float)]
 
 
+class Region(Structure):
+    """nafgpu_region: letters [start, end) of record `record`; end = REGION_END: the record's length."""
+    _fields_ = [("record", c_uint64), ("start", c_uint64), ("end", c_uint64), ("reverse_complement", c_uint8), ("reserved", c_uint8 * 7)]
+
+
+REGION_END = 2 ** 64 - 1
+NOT_FOUND = 2 ** 64 - 1          # nafgpu_find_records: no record has this id
+
+
+class SelectOpts(Structure):
+    _fields_ = [("name_regions", c_uint8), ("reserved", c_uint8 * 7)]
+
+
+class SelectResult(Structure):
+    """nafgpu_select_result: `src` is what nafgpu_encode_device takes."""
+    _fields_ = [("src", EncodeSource), ("d_id_end", c_void_p), ("d_comment_end", c_void_p), ("n_regions", c_uint64), ("ms", c_float)]
+
+
 READ_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, POINTER(c_uint8), c_uint64)
 SEEK_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, c_int64, c_int)
 
@@ -123,6 +141,8 @@ EXPORTS = [
     "nafgpu_zstd_compress", "nafgpu_encoder_set_device", "nafgpu_encode_device", "nafgpu_encode_free", "nafgpu_encode_last_times",
     "nafgpu_parse_opts_default", "nafgpu_parse_text", "nafgpu_parse_copy_to_host", "nafgpu_parse_hash64", "nafgpu_parse_free",
     "nafgpu_encode_text", "nafgpu_zstd_compress_lz",
+    "nafgpu_select", "nafgpu_find_records", "nafgpu_selection_format", "nafgpu_selection_copy_to_host", "nafgpu_selection_hash64",
+    "nafgpu_selection_free",
 ]
 
 
@@ -211,6 +231,15 @@ class Library:
             L.nafgpu_parse_free.restype = None
             L.nafgpu_encode_text.argtypes = [c_void_p, c_uint64, POINTER(ParseOpts), POINTER(EncoderOpts), c_int, c_int,
                                              POINTER(c_void_p), POINTER(c_uint64), POINTER(Error)]
+        if hasattr(L, "nafgpu_select"):                      # (absent from older builds loaded for A/B runs)
+            L.nafgpu_select.argtypes = [c_void_p, POINTER(Region), c_uint64, POINTER(SelectOpts), POINTER(c_void_p), POINTER(SelectResult),
+                                        POINTER(Error)]
+            L.nafgpu_find_records.argtypes = [c_void_p, c_char_p, c_uint64, c_uint64, POINTER(c_uint64), POINTER(Error)]
+            L.nafgpu_selection_format.argtypes = [c_void_p, c_uint64, POINTER(TextResult)]
+            L.nafgpu_selection_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
+            L.nafgpu_selection_hash64.argtypes = [c_void_p, c_void_p, c_uint64, c_uint64, POINTER(c_uint64)]
+            L.nafgpu_selection_free.argtypes = [c_void_p]
+            L.nafgpu_selection_free.restype = None
 
     # ---- helpers ---------------------------------------------------------------------------
     def zstd_decompress(self, payload: bytes, size: int, device: int = -1) -> bytes:

@@ -24,6 +24,7 @@
 #include "container.h"
 #include "engine.h"
 #include "hash64.h"
+#include "select.h"
 
 using namespace nafgpu;
 
@@ -472,6 +473,62 @@ void fill_result(nafgpu_decoder *d, nafgpu_device_result *out) {
 }
 
 }  // namespace
+
+// ---- what nafgpu_select / nafgpu_find_records (select.cpp) need of a decoder -----------------------------------------
+namespace nafgpu {
+namespace sel {
+
+Failure decoder_source(nafgpu_decoder *d, bool need_lengths, SelSource *out) {
+    if (d->opts.shard_count > 1 || d->opts.shard_protocol) return Failure::make(NAFGPU_E_INVALID_ARG, "a selection is not available on a shard");
+    if (d->decoded && d->tiled_output) d->decoded = false;                 // the whole output in HBM, as for text
+    Failure f = ensure_decoded(d, false);
+    if (!f.ok()) return f;
+    for (int s = 0; s < kNumSections; s++)
+        if (d->use[s] && !d->job.section_failure(s).ok()) return d->job.section_failure(s);
+    const ArchiveJob &j = d->job;
+    if (j.job(kSequence).ready() && j.job(kSequence).sharded()) return Failure::make(NAFGPU_E_INVALID_ARG, "a selection is not available on a shard");
+    if (j.job(kSequence).tiled_output() || j.job(kQuality).tiled_output())
+        return Failure::make(NAFGPU_E_INVALID_ARG, "a selection needs the whole sequence in HBM (tiled output is for the record iterator)");
+    if (need_lengths && (!d->use[kLengths] || !j.job(kLengths).ready()))
+        return Failure::make(NAFGPU_E_INVALID_ARG, "a selection needs the Length section");
+    const bool nuc = d->header.sequence_type <= 1;
+    *out = SelSource();
+    if (d->use[kSequence] && j.job(kSequence).ready()) {
+        out->seq = j.d_sequence();
+        out->n_seq = nuc ? std::min<uint64_t>(j.n_sequence_bytes(), d->sec[kSequence].present ? d->sec[kSequence].original_size : 0)
+                         : j.job(kSequence).total_size();
+    }
+    if (d->use[kQuality] && j.job(kQuality).ready()) {
+        out->qual = j.d_section(kQuality);
+        out->n_qual = j.section_size(kQuality);
+    }
+    if (d->use[kLengths] && j.job(kLengths).ready()) {
+        out->rec_end = j.d_rec_ends();
+        out->n_rec = std::min<uint64_t>(d->header.number_of_sequences, j.n_records());
+    }
+    if (d->use[kIds] && j.job(kIds).ready()) {
+        out->ids = j.d_section(kIds);
+        out->id_end = j.d_id_ends();
+        out->n_ids = j.n_ids();
+    }
+    if (d->use[kComments] && j.job(kComments).ready()) {
+        out->com = j.d_section(kComments);
+        out->com_end = j.d_com_ends();
+        out->n_com = j.n_comments();
+    }
+    out->sequence_type = d->header.sequence_type;
+    out->name_separator = d->header.name_separator;
+    out->device = j.device();
+    return Failure();
+}
+
+int decoder_fail(nafgpu_decoder *d, const Failure &f, nafgpu_error *err) {
+    d->last = f;
+    return fail_c(err, f);
+}
+
+}  // namespace sel
+}  // namespace nafgpu
 
 extern "C" {
 

@@ -296,6 +296,120 @@ class Decoder:
             raise RuntimeError("nafgpu_hash64_device failed: %d" % rc)
         return out.value
 
+    # ---- records and regions on the device (include/nafgpu.h: nafgpu_select has the rules) ----
+    def _raise_select(self, rc, err):
+        if rc == _ffi.E_INVALID_ARG:
+            raise ValueError(err.message.decode("utf-8", "replace"))
+        _raise(err)
+
+    def find(self, names):
+        """-> for every name (str or bytes) the index of the first record with that id, or None; looked up on the GPU."""
+        blobs = [n.encode("utf-8") if isinstance(n, str) else bytes(n) for n in names]
+        if any(b"\0" in b for b in blobs):
+            raise ValueError("a name holds a NUL byte")
+        blob = b"".join(b + b"\0" for b in blobs)
+        out, err = (ctypes.c_uint64 * max(len(blobs), 1))(), _ffi.Error()
+        rc = self._lib.c.nafgpu_find_records(self._h, blob, len(blob), len(blobs), out, byref(err))
+        if rc != _ffi.OK:
+            self._raise_select(rc, err)
+        return [None if v == _ffi.NOT_FOUND else int(v) for v in out[:len(blobs)]]
+
+    def select(self, regions, *, name_regions=False):
+        """Records and regions -> a Selection in HBM; region k becomes its record k.  A region is an int (a whole record),
+        (record, start, end) with end=None for the record's length, or (record, start, end, "-") for the reverse strand
+        (reversed and complemented; "+" is the forward one); `record` may be a name (str / bytes), resolved through find():
+        KeyError when no record has it.  name_regions: every id becomes id:START-END (1-based, inclusive) and id:START-END/rc.
+        ValueError for what the rules refuse."""
+        regions = [r if isinstance(r, (tuple, list)) else (r, 0, None) for r in regions]
+        named = sorted({r[0] for r in regions if isinstance(r[0], (str, bytes))}, key=repr)
+        index = dict(zip(named, self.find(named))) if named else {}
+        arr = (_ffi.Region * max(len(regions), 1))()
+        for k, r in enumerate(regions):
+            if len(r) not in (3, 4) or (len(r) == 4 and r[3] not in ("+", "-")):
+                raise ValueError("a region is an int, (record, start, end) or (record, start, end, '+' | '-'): %r" % (r,))
+            record = r[0]
+            if isinstance(record, (str, bytes)):
+                record = index[record]
+                if record is None:
+                    raise KeyError(r[0])
+            if int(record) < 0 or int(r[1]) < 0 or (r[2] is not None and int(r[2]) < 0):
+                raise ValueError("negative value in region %d: %r" % (k, r))
+            arr[k].record, arr[k].start = int(record), int(r[1])
+            arr[k].end = _ffi.REGION_END if r[2] is None else int(r[2])
+            arr[k].reverse_complement = int(len(r) == 4 and r[3] == "-")
+        opts = _ffi.SelectOpts(name_regions=int(bool(name_regions)))
+        h, res, err = c_void_p(), _ffi.SelectResult(), _ffi.Error()
+        rc = self._lib.c.nafgpu_select(self._h, arr, len(regions), byref(opts), byref(h), byref(res), byref(err))
+        if rc != _ffi.OK:
+            self._raise_select(rc, err)
+        return Selection(self._lib, h, res)
+
+
+class Selection:
+    """What Decoder.select() returns: records cut out of a decoded archive, in HBM, with the fields encode_device() reads
+    (d_sequence / n_bases, d_quality / n_quality, d_record_end / n_records, d_ids / n_ids_bytes, d_comments /
+    n_comments_bytes; None for a field the decoder did not decode), d_id_end / d_comment_end (as decode_all_device() gives
+    them), n_regions and ms (the selection kernels).  A copy: it outlives the decoder; the device buffers live until close()."""
+
+    def __init__(self, lib, handle, res):
+        self._lib, self._h = lib, handle
+        for name, _ in _ffi.EncodeSource._fields_:
+            value = getattr(res.src, name)
+            setattr(self, name, (value or None) if name.startswith("d_") else value)
+        self.d_id_end, self.d_comment_end = res.d_id_end or None, res.d_comment_end or None
+        self.n_regions, self.ms = res.n_regions, res.ms
+        self.fastq = self.d_quality is not None
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError("operation on closed selection.")
+        return self._h
+
+    def format_device(self, line_length=60):
+        """FASTA (FASTQ when the selection has qualities) text of the selected records, built on the GPU in lines of
+        `line_length` letters (0: one line); returns the nafgpu_text_result struct (d_text lives until the next call / close())."""
+        res = _ffi.TextResult()
+        rc = self._lib.c.nafgpu_selection_format(self._handle(), int(line_length), byref(res))
+        if rc == _ffi.E_INVALID_ARG:
+            raise ValueError("text output needs the sequence field")
+        if rc != _ffi.OK:
+            raise _ffi.NafError(rc, message="formatting a selection failed")
+        return res
+
+    def to_text(self, line_length=60):
+        res = self.format_device(line_length)
+        return self.copy_to_host(res.d_text, res.n_text)
+
+    def copy_to_host(self, d_ptr, n):
+        buf = ctypes.create_string_buffer(max(int(n), 1))
+        if self._lib.c.nafgpu_selection_copy_to_host(self._handle(), d_ptr, int(n), buf) != _ffi.OK:
+            raise _ffi.NafError(_ffi.E_DEVICE, message="device-to-host copy failed")
+        return buf.raw[:int(n)]
+
+    def hash_device(self, d_ptr, n, first_chunk=0):
+        out = ctypes.c_uint64()
+        if self._lib.c.nafgpu_selection_hash64(self._handle(), d_ptr, int(n), int(first_chunk), byref(out)) != _ffi.OK:
+            raise _ffi.NafError(_ffi.E_DEVICE, message="hashing a device buffer failed")
+        return out.value
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            self._lib.c.nafgpu_selection_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc_value, traceback):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 def open(file, mode="r", **options):
     """nafcodec.open (lib.pyi:89-108, nafcodec/__init__.py): "r" -> Decoder, "w" -> Encoder."""
