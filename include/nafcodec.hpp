@@ -5,6 +5,7 @@
 #pragma once
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -405,6 +406,81 @@ inline std::string encode_text(const std::string &text, const EncoderBuilder &fi
     nafgpu_encode_free(p);
     return out;
 }
+
+// (no counterpart in the reference) per-record letter counts, quality sums and the sections' histograms of records that are
+// in HBM, counted on the GPU: nafgpu_summarize has the rules.  A Summary owns its device buffers and outlives its source;
+// the accessors copy a table to the host (empty when the source has no field for it).  Move-only.
+class Summary {
+public:
+    enum Column { A = 0, C, G, T, N, Iupac, Other, Lower };   // the columns of the default table
+    Summary(Summary &&o) noexcept : s_(std::exchange(o.s_, nullptr)), res_(o.res_) {}
+    Summary &operator=(Summary &&o) noexcept {
+        if (this != &o) {
+            nafgpu_summary_free(s_);
+            s_ = std::exchange(o.s_, nullptr);
+            res_ = o.res_;
+        }
+        return *this;
+    }
+    Summary(const Summary &) = delete;
+    ~Summary() { nafgpu_summary_free(s_); }
+
+    const nafgpu_summary_result &result() const { return res_; }
+    uint64_t n_records() const { return res_.n_records; }
+    std::vector<uint64_t> totals() const { return std::vector<uint64_t>(res_.totals, res_.totals + 8); }
+    uint64_t quality_total() const { return res_.quality_total; }
+    float ms() const { return res_.ms; }
+    std::vector<uint64_t> counts() const { return words(res_.d_counts, 8 * res_.n_records); }   // n_records rows of 8 columns
+    std::vector<uint64_t> quality_sum() const { return words(res_.d_quality_sum, res_.n_records); }
+    std::vector<uint64_t> letter_hist() const { return words(res_.d_letter_hist, 256); }
+    std::vector<uint64_t> quality_hist() const { return words(res_.d_quality_hist, 256); }
+
+    // classes: null = the default table, else 256 masks of eight columns
+    static Summary of(const nafgpu_encode_source &src, int device = -1, const uint8_t *classes = nullptr) {
+        nafgpu_summary_opts o = options(classes);
+        nafgpu_summary *s = nullptr;
+        nafgpu_summary_result r;
+        nafgpu_error e{};
+        if (nafgpu_summarize(&src, &o, device, &s, &r, &e) != NAFGPU_OK) throw Error(e);
+        return Summary(s, r);
+    }
+    static Summary of(const Decoder &dec, const uint8_t *classes = nullptr) {
+        nafgpu_summary_opts o = options(classes);
+        nafgpu_summary *s = nullptr;
+        nafgpu_summary_result r;
+        nafgpu_error e{};
+        if (nafgpu_summarize_decoder(dec.raw(), &o, &s, &r, &e) != NAFGPU_OK) throw Error(e);
+        return Summary(s, r);
+    }
+
+private:
+    Summary(nafgpu_summary *s, const nafgpu_summary_result &r) : s_(s), res_(r) {}
+    static nafgpu_summary_opts options(const uint8_t *classes) {
+        nafgpu_summary_opts o{};
+        if (classes) {
+            std::memcpy(o.classes, classes, 256);
+            o.use_classes = 1;
+        }
+        return o;
+    }
+    std::vector<uint64_t> words(const uint64_t *d_ptr, uint64_t n) const {
+        std::vector<uint64_t> out(d_ptr ? static_cast<size_t>(n) : 0);
+        const int rc = out.empty() ? NAFGPU_OK : nafgpu_summary_copy_to_host(s_, d_ptr, 8 * n, out.data());
+        if (rc != NAFGPU_OK) {
+            nafgpu_error e{};
+            e.status = rc;
+            std::snprintf(e.message, sizeof e.message, "nafgpu_summary_copy_to_host: %s", rc == NAFGPU_E_DEVICE ? "the copy failed" : "a null argument");
+            throw Error(e);
+        }
+        return out;
+    }
+    nafgpu_summary *s_ = nullptr;
+    nafgpu_summary_result res_{};
+};
+// decodes first if nothing is decoded yet
+inline Summary summarize(const Decoder &dec, const uint8_t *classes = nullptr) { return Summary::of(dec, classes); }
+inline Summary summarize(const Selection &sel, int device = -1, const uint8_t *classes = nullptr) { return Summary::of(sel.source(), device, classes); }
+inline Summary summarize(const nafgpu_encode_source &src, int device, const uint8_t *classes = nullptr) { return Summary::of(src, device, classes); }
 
 // (no counterpart in the reference: the library keeps device memory of closed decoders for the next one -- nafgpu.h)
 inline void trim_device_memory(int device = -1) { (void)nafgpu_trim_device_memory(device); }

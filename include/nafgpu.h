@@ -510,6 +510,51 @@ int nafgpu_selection_copy_to_host(nafgpu_selection *sel, const void *d_ptr, uint
 int nafgpu_selection_hash64(nafgpu_selection *sel, const void *d_ptr, uint64_t n, uint64_t first_chunk, uint64_t *out);
 void nafgpu_selection_free(nafgpu_selection *sel);
 
+/* ---- records in HBM -> a small table per record: letter counts, GC, N, soft-masked letters, quality sums (the numbers a
+ * user picks records by before nafgpu_select; what `unnaf --charcount` prints) ----
+ * The counting runs in HIP kernels (summary.hip); the letters stay in HBM, the tables are a few bytes per record.  The
+ * reference has no counterpart.  Rules:
+ *   classes   classes[b] is a mask of eight bits: a letter with byte value b adds 1 to every column whose bit is set, so
+ *             columns may overlap.  opts == NULL or use_classes == 0: the default table
+ *                 column 0  A a      1  C c      2  G g      3  T t U u      4  N n
+ *                        5  the other IUPAC codes R Y K M S W B D H V, both cases
+ *                        6  every byte that is in none of columns 0-5, '-' included
+ *                        7  a .. z (lower case), in addition to the letter's own column
+ *             under which columns 0-6 of a row add up to the record's length, whatever the bytes are.
+ *   shape     record k is letters [d_record_end[k-1], d_record_end[k]); the same slice of d_quality gives d_quality_sum[k].
+ *             Empty records have rows of zeros.  Letters behind the last record end count in the histograms only.
+ *             d_record_end == NULL or n_records == 0: histograms only.  d_ids and d_comments are ignored.  All positions and
+ *             counters are 64-bit; integer work only, so the result is exact whatever the schedule.
+ *   totals    the column sums over all records (of the whole section when there is no record table).
+ *   refusals  NAFGPU_E_INVALID_ARG: src, out or res NULL, or both d_sequence and d_quality NULL.  NAFGPU_E_INVALID_LENGTH:
+ *             both sections given and n_quality != n_bases; a record end below the one in front of it or beyond the section
+ *             -- checked on the device, the message names the LOWEST offending record, and no kernel reads outside the
+ *             section whatever the table holds.  nafgpu_summarize_decoder decodes first if nothing is decoded yet, makes the
+ *             checks of nafgpu_format_device (shard, tiled output, a section that failed), does not need the Length section
+ *             (without it: histograms only) and returns NAFGPU_E_IO / NAFGPU_IO_UNEXPECTED_EOF when the last record end lies
+ *             beyond what was decoded; its error is also kept for nafgpu_last_error.  NAFGPU_E_DEVICE: an allocation, copy
+ *             or kernel failed.  On any error nothing is produced. */
+typedef struct { uint8_t classes[256]; uint8_t use_classes; uint8_t reserved[7]; } nafgpu_summary_opts;
+typedef struct nafgpu_summary nafgpu_summary;          /* owns its device buffers, like nafgpu_selection; it outlives its source */
+typedef struct {
+    const uint64_t *d_counts;        /* n_records rows of 8 columns, row-major, 16-byte aligned (NULL without d_sequence or records) */
+    const uint64_t *d_quality_sum;   /* n_records entries: sum of the record's quality bytes (NULL without d_quality or records) */
+    const uint64_t *d_letter_hist;   /* 256 entries: how often each byte value occurs in d_sequence[0, n_bases) (NULL without it) */
+    const uint64_t *d_quality_hist;  /* 256 entries over d_quality[0, n_quality) */
+    uint64_t n_records, n_bases, n_quality;
+    uint64_t totals[8];              /* column sums over all records, computed on the host from d_letter_hist and the table */
+    uint64_t quality_total;
+    float ms;                        /* the summary kernels, HIP events */
+} nafgpu_summary_result;
+/* device -1 = current */
+int nafgpu_summarize(const nafgpu_encode_source *src, const nafgpu_summary_opts *opts, int device,
+                     nafgpu_summary **out, nafgpu_summary_result *res, nafgpu_error *err);
+int nafgpu_summarize_decoder(nafgpu_decoder *dec, const nafgpu_summary_opts *opts,
+                             nafgpu_summary **out, nafgpu_summary_result *res, nafgpu_error *err);
+/* n bytes from a pointer of the result; NAFGPU_E_INVALID_ARG: a NULL argument, NAFGPU_E_DEVICE: the copy failed */
+int nafgpu_summary_copy_to_host(nafgpu_summary *s, const void *d_ptr, uint64_t n, void *dst);
+void nafgpu_summary_free(nafgpu_summary *s);
+
 /* order-sensitive 64-bit checksum used for full-size parity checks: sum over the 8-byte words w_j of
  * mix64(w_j ^ (j + 1) * K) -- every word is mixed non-linearly with its position before it is added, so
  * byte errors cannot cancel -- see hash64.h */

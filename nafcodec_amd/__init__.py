@@ -5,11 +5,12 @@ Python mirror of the reference's public surface for the decode path
 All decoding happens on the GPU inside libnafgpu.so (include/nafgpu.h); there is no CPU path."""
 from .decoder import Decoder, Record, Selection, open  # noqa: F401
 from .encoder import Encoder, encode_device, encode_text, parse_text, zstd_compress  # noqa: F401
+from .summary import Summary, summarize  # noqa: F401
 from ._ffi import NafError  # noqa: F401
 
 __version__ = "0.1.0"
 __all__ = ["Decoder", "Encoder", "Record", "open", "NafError", "trim_device_memory", "encode_device", "zstd_compress",
-           "parse_text", "encode_text", "Selection"]
+           "parse_text", "encode_text", "Selection", "Summary", "summarize"]
 
 
 def trim_device_memory(device=-1):

@@ -123,6 +123,17 @@ class SelectResult(Structure):
     _fields_ = [("src", EncodeSource), ("d_id_end", c_void_p), ("d_comment_end", c_void_p), ("n_regions", c_uint64), ("ms", c_float)]
 
 
+class SummaryOpts(Structure):
+    """nafgpu_summary_opts: classes[b] = the columns (a mask of eight bits) a letter with byte value b counts in."""
+    _fields_ = [("classes", c_uint8 * 256), ("use_classes", c_uint8), ("reserved", c_uint8 * 7)]
+
+
+class SummaryResult(Structure):
+    _fields_ = [("d_counts", c_void_p), ("d_quality_sum", c_void_p), ("d_letter_hist", c_void_p), ("d_quality_hist", c_void_p),
+                ("n_records", c_uint64), ("n_bases", c_uint64), ("n_quality", c_uint64), ("totals", c_uint64 * 8),
+                ("quality_total", c_uint64), ("ms", c_float)]
+
+
 READ_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, POINTER(c_uint8), c_uint64)
 SEEK_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, c_int64, c_int)
 
@@ -143,6 +154,7 @@ EXPORTS = [
     "nafgpu_encode_text", "nafgpu_zstd_compress_lz",
     "nafgpu_select", "nafgpu_find_records", "nafgpu_selection_format", "nafgpu_selection_copy_to_host", "nafgpu_selection_hash64",
     "nafgpu_selection_free",
+    "nafgpu_summarize", "nafgpu_summarize_decoder", "nafgpu_summary_copy_to_host", "nafgpu_summary_free",
 ]
 
 
@@ -240,6 +252,13 @@ class Library:
             L.nafgpu_selection_hash64.argtypes = [c_void_p, c_void_p, c_uint64, c_uint64, POINTER(c_uint64)]
             L.nafgpu_selection_free.argtypes = [c_void_p]
             L.nafgpu_selection_free.restype = None
+        if hasattr(L, "nafgpu_summarize"):                   # (absent from older builds loaded for A/B runs)
+            L.nafgpu_summarize.argtypes = [POINTER(EncodeSource), POINTER(SummaryOpts), c_int, POINTER(c_void_p), POINTER(SummaryResult),
+                                           POINTER(Error)]
+            L.nafgpu_summarize_decoder.argtypes = [c_void_p, POINTER(SummaryOpts), POINTER(c_void_p), POINTER(SummaryResult), POINTER(Error)]
+            L.nafgpu_summary_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
+            L.nafgpu_summary_free.argtypes = [c_void_p]
+            L.nafgpu_summary_free.restype = None
 
     # ---- helpers ---------------------------------------------------------------------------
     def zstd_decompress(self, payload: bytes, size: int, device: int = -1) -> bytes:

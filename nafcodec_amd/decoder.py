@@ -344,6 +344,12 @@ class Decoder:
             self._raise_select(rc, err)
         return Selection(self._lib, h, res)
 
+    def summarize(self, classes=None):
+        """Per-record letter counts, quality sums and the sections' histograms of the decoded records, counted on the GPU
+        (decodes first if nothing is decoded yet) -> a Summary.  `classes`: 256 bytes, see nafcodec_amd.summary."""
+        from .summary import _summarize_decoder
+        return _summarize_decoder(self, classes)
+
 
 class Selection:
     """What Decoder.select() returns: records cut out of a decoded archive, in HBM, with the fields encode_device() reads
@@ -391,6 +397,12 @@ class Selection:
         if self._lib.c.nafgpu_selection_hash64(self._handle(), d_ptr, int(n), int(first_chunk), byref(out)) != _ffi.OK:
             raise _ffi.NafError(_ffi.E_DEVICE, message="hashing a device buffer failed")
         return out.value
+
+    def summarize(self, classes=None, *, device=None):
+        """Per-record letter counts and quality sums of the selected records -> a Summary (nafcodec_amd.summary)."""
+        from .summary import summarize
+        self._handle()
+        return summarize(self, classes, device=device, _lib=self._lib)
 
     def close(self):
         if self._h is not None:

@@ -211,6 +211,12 @@ class ParsedText:
             raise _ffi.NafError(_ffi.E_DEVICE, message="hashing a device buffer failed")
         return out.value
 
+    def summarize(self, classes=None, *, device=None):
+        """Per-record letter counts and quality sums of the parsed records -> a Summary (nafcodec_amd.summary)."""
+        from .summary import summarize
+        self._handle()
+        return summarize(self, classes, device=device, _lib=self._lib)
+
     def close(self):
         if self._h is not None:
             h, self._h = self._h, None
