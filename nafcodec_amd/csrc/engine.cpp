@@ -176,6 +176,8 @@ Failure SectionJob::prepare(const uint8_t *host_payload, size_t n, uint64_t expe
         const char *fs = hook_env("NAFGPU_HUF_SPLIT");     // tests: that many parts per stream whatever the size (0: never)
         const uint32_t force = fs ? static_cast<uint32_t>(std::atoi(fs)) : 0u;
         set_huf_split(fs && force == 0 ? 0u : lanes, force);
+        const char *ff = hook_env("NAFGPU_HUF_FLAT");      // tests, A/B runs: 0 keeps flat trees on k_huf_decode
+        set_huf_flat(!(ff && ff[0] == '0'));
     }
     const double t0 = now_ms();
     if (walked_payload_ != host_payload || walked_n_ != n) walk(host_payload, n);

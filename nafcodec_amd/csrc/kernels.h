@@ -88,6 +88,12 @@ void launch_huf_decode(hipStream_t stream, const uint8_t *src, const HufTask *ta
                        const uint64_t *blk_base, uint8_t *out, uint8_t *lit, const SeqBlock *seq_blocks, const Seq *seqs,
                        const uint8_t *dicts, bool ascii, uint32_t t_char, uint32_t *status);
 
+// K1 for classes of kind kTblFlat (huf_flat.hip): every code of a stream has the same length, the streams are decoded
+// as a gather -- one workgroup per stream, aligned 16-byte stores.  launch_huf_decode passes such classes on to it.
+void launch_huf_flat(hipStream_t stream, const uint8_t *src, const HufTask *tasks, const HufClass &cls, const HufTblCopy *copies,
+                     const HufStream *streams, const uint16_t *pool, const uint64_t *blk_base, uint8_t *out, uint8_t *lit,
+                     bool ascii, uint32_t t_char, uint32_t *status);
+
 // K4: LZ77 sequence execution: repeat-offset chain, parallel literal scatter, then -- all enqueued at once, no host
 // round trip: every stage returns at once when the one before it left nothing --
 //   dense sections (pj_dist != null: matches are a good part of the output): every element learns the distance to the

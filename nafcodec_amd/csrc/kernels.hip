@@ -4228,6 +4228,10 @@ void launch_huf_decode(hipStream_t stream, const uint8_t *src, const HufTask *ta
                        const uint64_t *blk_base, uint8_t *out, uint8_t *lit, const SeqBlock *seq_blocks, const Seq *seqs,
                        const uint8_t *dicts, bool ascii, uint32_t t_char, uint32_t *status) {
     if (!cls.n_tasks) return;
+    if (cls.tbl == kTblFlat) {                             // codes of one length: a gather, not a walk (huf_flat.hip)
+        launch_huf_flat(stream, src, tasks, cls, copies, streams, pool, blk_base, out, lit, ascii, t_char, status);
+        return;
+    }
     const uint32_t lds = (cls.lds_bytes + 15u) & ~15u;
     const bool a = ascii && !cls.to_lit;                   // the literal buffer always holds packed bytes
     const HufTask *t0 = tasks + cls.first_task;

@@ -67,7 +67,7 @@ struct HufTblCopy {      // build the two-symbol table of pool[pool_off ..) at L
     uint32_t bits;       // max_bits | W << 8
 };
 
-// One workgroup of k_huf_decode: <= 64 streams and the decode tables of their trees.  Tasks come in three
+// One workgroup of k_huf_decode: <= 64 streams and the decode tables of their trees.  Tasks come in four
 // table formats, launched separately:
 //   kTblBaked   8-byte entries with the output characters baked in (one tree per task: the fast path)
 //   kTblCompact 4-byte entries {sym1, sym2, bits, bits of sym1, two} whose characters come from a 512-byte
@@ -77,7 +77,12 @@ struct HufTblCopy {      // build the two-symbol table of pool[pool_off ..) at L
 //               real genomes give: what counts there is LDS per lane, because the lanes resident per CU set
 //               the throughput; and a dictionary shared by the wave is read conflict-free -- the few hot
 //               symbols are broadcast)
-enum HufTblKind : uint32_t { kTblBaked = 0, kTblCompact = 1, kTblDict = 2 };
+//   kTblFlat    no staged table and no lane per stream: every tree of the task has 2^L symbols, so all its codes are L
+//               bits long and symbol j of a stream lies L (j + 1) bits below the end mark.  k_huf_flat (huf_flat.hip)
+//               decodes such streams as a gather, one workgroup per stream.  HufStream::max_bits holds L,
+//               HufStream::tbl_lds the index of the stream's tree among the task's HufTblCopy records (of which only
+//               pool_off is used).  Whole streams only (no SEG, no parts).
+enum HufTblKind : uint32_t { kTblBaked = 0, kTblCompact = 1, kTblDict = 2, kTblFlat = 3 };
 struct HufTask {
     uint32_t first_stream, n_streams, first_copy, n_copies;
     uint32_t dict_off;       // kTblDict: first of the task's kHufDictSyms dictionary symbols in the dictionary pool (short codes first)

@@ -673,6 +673,13 @@ static uint32_t g_dict_slots = kHufLdsSlots2;
 // (8 376 streams: 2.8 -> 4.4 ms): below kHufSplitMin parts a section is left alone.  `g_split_force`: tests.
 constexpr uint32_t kHufSplitMin = 8;
 static uint32_t g_split_target = 0, g_split_force = 0;
+// Flat trees (plan.h: kTblFlat).  A Huffman tree is complete, so one with 2^max_bits symbols gives them all codes of
+// max_bits bits: where a symbol lies then follows from its number alone, and k_huf_flat decodes the streams as a gather
+// at the rate of memory.  A stream qualifies when its tree is flat, it is not interleaved with matches (flags & 2) and
+// the section is not cut into parts; qualifying streams are packed into tasks of their own (kTblFlat), everything else
+// goes through k_huf_decode as before.
+// `g_flat` off: never (tests that want k_huf_decode's baked path on such data; A/B runs).
+static bool g_flat = true;
 
 void pack_tasks(ZPlan *plan) {
     std::vector<HufRef> &stream_tbl = plan->stream_ref;
@@ -699,14 +706,18 @@ void pack_tasks(ZPlan *plan) {
         plan->streams.swap(parts);
         stream_tbl.swap(parts_tbl);
     }
-    {   // stable partition by destination
+    // a stream for k_huf_flat: whole, not interleaved with matches, every code of its tree max_bits long
+    auto stream_flat = [&](const HufStream &hs, const HufRef &t) -> bool {
+        return g_flat && split == 1 && !(hs.flags & 2) && t.max_bits >= 1 && t.max_bits <= 8 && t.n_syms == (1u << t.max_bits);
+    };
+    {   // stable partition by destination, and inside a destination by kernel (flat streams first): tasks stay full
         std::vector<HufStream> ordered;
         std::vector<HufRef> ordered_tbl;
         ordered.reserve(plan->streams.size());
         ordered_tbl.reserve(plan->streams.size());
-        for (int pass = 0; pass < 2; pass++)
+        for (int pass = 0; pass < 4; pass++)
             for (size_t s = 0; s < plan->streams.size(); s++)
-                if ((plan->streams[s].flags & 1) == pass) {
+                if ((plan->streams[s].flags & 1) == (pass >> 1) && stream_flat(plan->streams[s], stream_tbl[s]) == !(pass & 1)) {
                     ordered.push_back(plan->streams[s]);
                     ordered_tbl.push_back(stream_tbl[s]);
                 }
@@ -727,7 +738,7 @@ void pack_tasks(ZPlan *plan) {
     };
     struct Packed {
         HufTask task;
-        uint32_t key;        // to_lit << 3 | tbl << 1 | seg
+        uint32_t key;        // to_lit << 3 | tbl << 1 | seg   (tbl: two bits, kTblBaked .. kTblFlat)
         uint32_t lds_bytes;
         uint32_t sync_lds;   // one length byte per entry of the task's trees (k_huf_sync / k_huf_bounds)
     };
@@ -760,6 +771,10 @@ void pack_tasks(ZPlan *plan) {
                     bool seen = false;
                     for (const HufRef &d : distinct) seen = seen || d.pool_off == stream_tbl[k].pool_off;
                     if (!seen) distinct.push_back(stream_tbl[k]);
+                }
+                if (stream_flat(plan->streams[s], stream_tbl[s])) {   // (so are all of the group) nothing to stage, nothing to budget
+                    kind = kTblFlat;
+                    break;
                 }
                 // the symbols the trees use between them: few enough for one shared dictionary?
                 bool small = distinct.size() > 1;
@@ -813,7 +828,12 @@ void pack_tasks(ZPlan *plan) {
             }
             uint32_t lds_used = 0;
             std::vector<uint32_t> lds_of(distinct.size());
-            for (size_t d = 0; d < distinct.size(); d++) {
+            for (size_t d = 0; kind == kTblFlat && d < distinct.size(); d++) {     // the kernel reads the pool entries themselves
+                const uint32_t mb = distinct[d].max_bits;
+                lds_of[d] = static_cast<uint32_t>(d);      // (HufStream::tbl_lds: which of the task's trees)
+                plan->tbl_copies.push_back(HufTblCopy{distinct[d].pool_off, 0, 1u << mb, mb | (mb << 8)});
+            }
+            for (size_t d = 0; kind != kTblFlat && d < distinct.size(); d++) {
                 const uint32_t n = per_tree + staged_entries(distinct[d], W);
                 lds_of[d] = lds_used;
                 plan->tbl_copies.push_back(HufTblCopy{distinct[d].pool_off, lds_used, n, distinct[d].max_bits | (W << 8)});
@@ -825,23 +845,27 @@ void pack_tasks(ZPlan *plan) {
                 while (distinct[d].pool_off != stream_tbl[k].pool_off) d++;
                 HufStream &hs = plan->streams[k];
                 hs.tbl_lds = static_cast<uint16_t>(lds_of[d]);
-                hs.max_bits = static_cast<uint8_t>(W);
-                const uint32_t esc_bits = stream_tbl[k].max_bits > W ? stream_tbl[k].max_bits - W : 0;
+                hs.max_bits = static_cast<uint8_t>(kind == kTblFlat ? stream_tbl[k].max_bits : W);
+                const uint32_t esc_bits = kind != kTblFlat && stream_tbl[k].max_bits > W ? stream_tbl[k].max_bits - W : 0;
                 hs.flags = static_cast<uint8_t>((hs.flags & 0x0F) | (esc_bits << 4));
                 seg = seg || (hs.flags & 2);
             }
             const uint32_t to_lit = plan->streams[s].flags & 1u;
             const uint32_t entry_bytes = kind == kTblBaked ? 8u : (kind == kTblDict ? 2u : 4u);
             uint32_t sync_lds = 0;
-            for (const HufRef &d : distinct) sync_lds += std::max<uint32_t>(16u, 1u << d.max_bits);
+            for (const HufRef &d : distinct) sync_lds += kind == kTblFlat ? 0u : std::max<uint32_t>(16u, 1u << d.max_bits);
             packed.push_back(Packed{task, (to_lit << 3) | (kind << 1) | (seg ? 1u : 0u), lds_used * entry_bytes, sync_lds});
             s = e;
         }
     };
-    size_t first_lit = 0;
-    while (first_lit < plan->streams.size() && !(plan->streams[first_lit].flags & 1)) first_lit++;
-    pack_group(0, first_lit);
-    pack_group(first_lit, plan->streams.size());
+    for (size_t g0 = 0; g0 < plan->streams.size();) {         // the groups of the partition above, each packed on its own
+        size_t g1 = g0 + 1;
+        while (g1 < plan->streams.size() && (plan->streams[g1].flags & 1) == (plan->streams[g0].flags & 1) &&
+               stream_flat(plan->streams[g1], stream_tbl[g1]) == stream_flat(plan->streams[g0], stream_tbl[g0]))
+            g1++;
+        pack_group(g0, g1);
+        g0 = g1;
+    }
     // A few tasks without segments beside many with (the last blocks of a real genome's section): they join the segment-aware
     // class -- its kernel takes a stream of a block without sequences as one segment -- instead of forming a class of their own:
     // a class of ONE task still takes a whole task's time (64 streams, one lane each: 2.5 ms), and behind the classes that
@@ -877,6 +901,7 @@ void set_huf_split(uint32_t target_lanes, uint32_t force) {
     g_split_target = target_lanes;
     g_split_force = force >= 2 && force <= kHufSplitMax && (force & (force - 1)) == 0 ? force : 0;
 }
+void set_huf_flat(bool on) { g_flat = on; }
 void set_task_lanes(uint32_t lanes) { g_task_lanes = lanes >= 4 && lanes <= static_cast<uint32_t>(kHufWave) ? lanes : kHufWave; }
 
 std::string walk_zstd(const uint8_t *payload, size_t n, ZPlan *master, bool *truncated) {

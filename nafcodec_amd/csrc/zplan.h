@@ -88,6 +88,7 @@ void pack_tasks_public(ZPlan *plan);
 // sub-streams (zplan.cpp: g_split_target): sections below `target_lanes` / 2 streams are cut; force: that many parts, always (tests)
 void set_huf_split(uint32_t target_lanes, uint32_t force);
 void set_dict_slots(uint32_t slots);   // LDS budget of a dictionary-format task in 2-byte slots (experiments)
+void set_huf_flat(bool on);            // off: no task takes kTblFlat (tests of k_huf_decode on flat trees; A/B runs)
 void set_task_lanes(uint32_t lanes);   // streams per K1 task (experiments; 64 otherwise)
 // walk + (shard) + select: the whole section, or one shard of it, in one call
 std::string build_zplan(const uint8_t *payload, size_t n, ZPlan *plan, bool *truncated, uint32_t shard_rank = 0,
