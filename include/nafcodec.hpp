@@ -125,6 +125,85 @@ private:
     nafgpu_select_result res_{};
 };
 
+// (no counterpart in the reference) where patterns occur in records that are in HBM, matched on the GPU: nafgpu_search has the
+// rules.  SearchOptions: alphabet -1 = by the archive for Decoder::search (nucleotide for dna and rna, bytes for protein and
+// text) and nucleotide elsewhere; both_strands -1 = on for the nucleotide alphabet.
+struct SearchOptions {
+    int alphabet = -1;               // 0 nucleotide (IUPAC sets), 1 bytes (exact)
+    int both_strands = -1;
+    unsigned max_mismatches = 0;     // 0 .. 3 substitutions
+    uint64_t max_hits = 0;           // 0: no cap
+};
+// What search returns: a Hits owns its device buffers and outlives its source; the accessors copy a table to the host.  Hits
+// come in ascending order of (position, pattern, strand).  Move-only.
+class Hits {
+public:
+    Hits(Hits &&o) noexcept : h_(std::exchange(o.h_, nullptr)), res_(o.res_), n_patterns_(o.n_patterns_) {}
+    Hits &operator=(Hits &&o) noexcept {
+        if (this != &o) {
+            nafgpu_hits_free(h_);
+            h_ = std::exchange(o.h_, nullptr);
+            res_ = o.res_;
+            n_patterns_ = o.n_patterns_;
+        }
+        return *this;
+    }
+    Hits(const Hits &) = delete;
+    ~Hits() { nafgpu_hits_free(h_); }
+
+    const nafgpu_search_result &result() const { return res_; }
+    uint64_t n_hits() const { return res_.n_hits; }
+    uint64_t n_records() const { return res_.n_records; }
+    float ms() const { return res_.ms; }
+    std::vector<uint64_t> pattern_hits() const { return std::vector<uint64_t>(res_.pattern_hits, res_.pattern_hits + n_patterns_); }   // both strands
+    std::vector<nafgpu_region> regions() const { return table(res_.d_regions, res_.n_hits); }     // ready for nafgpu_select
+    std::vector<nafgpu_hit_info> info() const { return table(res_.d_info, res_.n_hits); }
+    std::vector<uint64_t> record_hit_begin() const { return table(res_.d_record_hit_begin, res_.n_records + 1); }   // CSR over the records
+
+    // dec null: `src` is searched; else the decoder (it decodes first if nothing is decoded yet)
+    static Hits of(nafgpu_decoder *dec, const nafgpu_encode_source *src, const std::vector<std::string> &patterns, const SearchOptions &opts, int device) {
+        std::string blob;
+        for (const std::string &p : patterns) blob.append(p).push_back('\0');
+        nafgpu_search_opts o{};
+        bool nucleotide = opts.alphabet != 1;
+        if (dec && opts.alphabet < 0) {
+            nafgpu_header h;
+            nafgpu_get_header(dec, &h);
+            nucleotide = h.sequence_type <= 1;
+        }
+        o.alphabet = nucleotide ? 0 : 1;
+        o.both_strands = opts.both_strands < 0 ? nucleotide : opts.both_strands != 0;
+        o.max_mismatches = static_cast<uint8_t>(opts.max_mismatches > 255 ? 255 : opts.max_mismatches);
+        o.max_hits = opts.max_hits;
+        nafgpu_hits *h = nullptr;
+        nafgpu_search_result r;
+        nafgpu_error e{};
+        const uint8_t *bytes = reinterpret_cast<const uint8_t *>(blob.data());
+        const int rc = dec ? nafgpu_search_decoder(dec, bytes, blob.size(), patterns.size(), &o, &h, &r, &e)
+                           : nafgpu_search(src, bytes, blob.size(), patterns.size(), &o, device, &h, &r, &e);
+        if (rc != NAFGPU_OK) throw Error(e);
+        return Hits(h, r, patterns.size());
+    }
+
+private:
+    Hits(nafgpu_hits *h, const nafgpu_search_result &r, size_t n_patterns) : h_(h), res_(r), n_patterns_(n_patterns) {}
+    template <class T>
+    std::vector<T> table(const T *d_ptr, uint64_t n) const {
+        std::vector<T> out(d_ptr ? static_cast<size_t>(n) : 0);
+        const int rc = out.empty() ? NAFGPU_OK : nafgpu_hits_copy_to_host(h_, d_ptr, sizeof(T) * n, out.data());
+        if (rc != NAFGPU_OK) {
+            nafgpu_error e{};
+            e.status = rc;
+            std::snprintf(e.message, sizeof e.message, "nafgpu_hits_copy_to_host: %s", rc == NAFGPU_E_DEVICE ? "the copy failed" : "a null argument");
+            throw Error(e);
+        }
+        return out;
+    }
+    nafgpu_hits *h_ = nullptr;
+    nafgpu_search_result res_{};
+    size_t n_patterns_ = 0;
+};
+
 class Decoder {   // mod.rs:285-461
 public:
     Decoder(Decoder &&o) noexcept
@@ -231,6 +310,20 @@ public:
         if (nafgpu_select(d_, regions.empty() ? nullptr : &regions[0].r, regions.size(), &o, &s, &r, &e) != NAFGPU_OK) throw Error(e);
         return Selection(s, r);
     }
+    // the hits of a search as records of their own, a reverse-strand hit reversed and complemented: every record reads as its
+    // pattern is written
+    Selection select(const Hits &hits, bool name_regions = false) {
+        const std::vector<nafgpu_region> regions = hits.regions();
+        nafgpu_select_opts o{};
+        o.name_regions = name_regions ? 1 : 0;
+        nafgpu_selection *s = nullptr;
+        nafgpu_select_result r;
+        nafgpu_error e{};
+        if (nafgpu_select(d_, regions.data(), regions.size(), &o, &s, &r, &e) != NAFGPU_OK) throw Error(e);
+        return Selection(s, r);
+    }
+    // (no counterpart in the reference) where `patterns` occur in the decoded records (decodes first if nothing is decoded yet)
+    Hits search(const std::vector<std::string> &patterns, const SearchOptions &opts = SearchOptions()) { return Hits::of(d_, nullptr, patterns, opts, -1); }
     nafgpu_decoder *raw() const { return d_; }
 
 private:
@@ -481,6 +574,13 @@ private:
 inline Summary summarize(const Decoder &dec, const uint8_t *classes = nullptr) { return Summary::of(dec, classes); }
 inline Summary summarize(const Selection &sel, int device = -1, const uint8_t *classes = nullptr) { return Summary::of(sel.source(), device, classes); }
 inline Summary summarize(const nafgpu_encode_source &src, int device, const uint8_t *classes = nullptr) { return Summary::of(src, device, classes); }
+
+inline Hits search(const Selection &sel, const std::vector<std::string> &patterns, const SearchOptions &opts = SearchOptions(), int device = -1) {
+    return Hits::of(nullptr, &sel.source(), patterns, opts, device);
+}
+inline Hits search(const nafgpu_encode_source &src, const std::vector<std::string> &patterns, const SearchOptions &opts = SearchOptions(), int device = -1) {
+    return Hits::of(nullptr, &src, patterns, opts, device);
+}
 
 // (no counterpart in the reference: the library keeps device memory of closed decoders for the next one -- nafgpu.h)
 inline void trim_device_memory(int device = -1) { (void)nafgpu_trim_device_memory(device); }

@@ -555,6 +555,78 @@ int nafgpu_summarize_decoder(nafgpu_decoder *dec, const nafgpu_summary_opts *opt
 int nafgpu_summary_copy_to_host(nafgpu_summary *s, const void *d_ptr, uint64_t n, void *dst);
 void nafgpu_summary_free(nafgpu_summary *s);
 
+/* ---- records in HBM -> where a primer, an adapter, a restriction site or a guide occurs, as regions for nafgpu_select (records
+ * picked by CONTENT, as nafgpu_find_records picks them by name and nafgpu_summarize by numbers) ----
+ * The matching runs in HIP kernels (search.hip); the letters stay in HBM, the answer is 40 bytes per hit and 8 per record.
+ * The reference has no counterpart.  Rules:
+ *   patterns  n_patterns (1 .. 16) NUL-terminated strings, concatenated, in n_bytes, as nafgpu_find_records takes its names;
+ *             each 1 .. 64 letters.
+ *   windows   record k is letters [d_record_end[k-1], d_record_end[k]).  A hit is a window of m = pattern-length letters that
+ *             lies inside ONE record: windows never cross a record end, a record shorter than the pattern (an empty one
+ *             included) has none, letters behind the last record end are not searched.  d_record_end == NULL or
+ *             n_records == 0: the whole section is record 0 (n_records of the result is 1).
+ *   alphabet  0, nucleotide: a letter's set is the format's 4-bit code -- A 1, C 2, G 4, T and U 8, N 15, the other IUPAC
+ *             codes their unions (R 5, Y 10, K 12, M 3, S 6, W 9, B 14, D 13, H 11, V 7); either case, so the soft mask is
+ *             ignored; every other byte, '-' included, has the empty set.  Pattern position j accepts a text byte when the
+ *             byte's set is not empty and a subset of the pattern letter's set: N in a pattern accepts every IUPAC letter, R
+ *             accepts A, G and R, and an N in the text is accepted by a pattern N only.
+ *             1, bytes: a position accepts exactly its own byte.
+ *   mismatches  the number of positions whose text byte is not accepted (substitutions: Hamming distance; no insertions or
+ *             deletions).  A window is a hit when that number is <= max_mismatches; it goes into nafgpu_hit_info.mismatches.
+ *   strands   with both_strands every pattern is also searched as its reverse complement: order reversed, every set with its
+ *             four bits reversed (the complement of nafgpu_select).  Such a hit is reported in forward coordinates with
+ *             reverse_complement = 1, so nafgpu_select of the region yields letters that match the pattern as written.  A
+ *             palindromic site (GAATTC) is reported once per strand at the same place; equal patterns given twice are
+ *             reported once each.
+ *   output    hits in ascending order of (absolute start position, pattern index, strand with + first); overlapping hits
+ *             are all reported.  d_regions[i] = {record, start, start + m, strand} with start relative to the record;
+ *             d_record_hit_begin is the CSR row table over that order, begin[n_records] = n_hits; pattern_hits[p] counts
+ *             both strands.  Zero hits: NAFGPU_OK with n_hits 0.  All positions and counts are 64-bit; integer work only,
+ *             so the result is exact whatever the schedule.
+ *   refusals  NAFGPU_E_INVALID_ARG: a NULL argument; n_patterns 0 or > 16; `patterns` not exactly n_patterns NUL-terminated
+ *             strings in n_bytes; a pattern that is empty or longer than 64; max_mismatches > 3 or >= the shortest
+ *             pattern's length; a nucleotide pattern letter outside ACGTURYKMSWBDHVN (either case); an alphabet other than 0
+ *             and 1; both_strands with the bytes alphabet; d_sequence == NULL; more than max_hits hits (the message gives
+ *             the count) -- where a pattern offends, the message names the LOWEST such pattern index.
+ *             NAFGPU_E_INVALID_LENGTH: a record end below the one in front of it or beyond the section -- checked on the
+ *             device, the message names the LOWEST offending record, and no kernel reads outside the section or the end
+ *             table whatever the table holds.  NAFGPU_E_DEVICE: an allocation, copy or kernel failed.
+ *             nafgpu_search_decoder decodes first if nothing is decoded yet, makes the checks of nafgpu_format_device (shard,
+ *             tiled output, a section that failed), does not need the Length section, and returns NAFGPU_E_IO /
+ *             NAFGPU_IO_UNEXPECTED_EOF for a record end beyond what was decoded; its error is also kept for
+ *             nafgpu_last_error.  With opts == NULL its alphabet comes from the archive's sequence type (nucleotide for DNA
+ *             and RNA, bytes for protein and text; one strand, no mismatches); an explicit alphabet 0 on a protein or text
+ *             archive is NAFGPU_E_INVALID_ARG.  nafgpu_search with opts == NULL: all options 0.
+ *             On any error nothing is produced. */
+#define NAFGPU_SEARCH_MAX_PATTERNS 16
+#define NAFGPU_SEARCH_MAX_LENGTH   64
+#define NAFGPU_SEARCH_MAX_MISMATCHES 3
+typedef struct {
+    uint8_t alphabet;            /* 0 = nucleotide (IUPAC sets, case and T/U ignored), 1 = bytes (exact) */
+    uint8_t both_strands;        /* nucleotide only: also report where the reverse complement of a pattern lies */
+    uint8_t max_mismatches;      /* 0..3 substitutions */
+    uint8_t reserved[5];
+    uint64_t max_hits;           /* 0: no cap; else more hits than this is a refusal */
+} nafgpu_search_opts;
+typedef struct { uint32_t pattern; uint8_t mismatches; uint8_t reserved[3]; } nafgpu_hit_info;
+typedef struct nafgpu_hits nafgpu_hits;                /* owns its device buffers, like nafgpu_summary; it outlives its source */
+typedef struct {
+    const nafgpu_region *d_regions;          /* n_hits regions, ready for nafgpu_select once copied to the host */
+    const nafgpu_hit_info *d_info;           /* n_hits */
+    const uint64_t *d_record_hit_begin;      /* n_records + 1: the hits of record k are [begin[k], begin[k + 1]) */
+    uint64_t n_hits, n_records, n_bases;
+    uint64_t pattern_hits[NAFGPU_SEARCH_MAX_PATTERNS];
+    float ms;                                /* the search kernels, HIP events */
+} nafgpu_search_result;
+/* device -1 = current; opts may be NULL */
+int nafgpu_search(const nafgpu_encode_source *src, const uint8_t *patterns, uint64_t n_bytes, uint64_t n_patterns,
+                  const nafgpu_search_opts *opts, int device, nafgpu_hits **out, nafgpu_search_result *res, nafgpu_error *err);
+int nafgpu_search_decoder(nafgpu_decoder *dec, const uint8_t *patterns, uint64_t n_bytes, uint64_t n_patterns,
+                          const nafgpu_search_opts *opts, nafgpu_hits **out, nafgpu_search_result *res, nafgpu_error *err);
+/* n bytes from a pointer of the result; NAFGPU_E_INVALID_ARG: a NULL argument, NAFGPU_E_DEVICE: the copy failed */
+int nafgpu_hits_copy_to_host(nafgpu_hits *h, const void *d_ptr, uint64_t n, void *dst);
+void nafgpu_hits_free(nafgpu_hits *h);
+
 /* order-sensitive 64-bit checksum used for full-size parity checks: sum over the 8-byte words w_j of
  * mix64(w_j ^ (j + 1) * K) -- every word is mixed non-linearly with its position before it is added, so
  * byte errors cannot cancel -- see hash64.h */

@@ -6,11 +6,12 @@ All decoding happens on the GPU inside libnafgpu.so (include/nafgpu.h); there is
 from .decoder import Decoder, Record, Selection, open  # noqa: F401
 from .encoder import Encoder, encode_device, encode_text, parse_text, zstd_compress  # noqa: F401
 from .summary import Summary, summarize  # noqa: F401
+from .search import Hits, search  # noqa: F401
 from ._ffi import NafError  # noqa: F401
 
 __version__ = "0.1.0"
 __all__ = ["Decoder", "Encoder", "Record", "open", "NafError", "trim_device_memory", "encode_device", "zstd_compress",
-           "parse_text", "encode_text", "Selection", "Summary", "summarize"]
+           "parse_text", "encode_text", "Selection", "Summary", "summarize", "Hits", "search"]
 
 
 def trim_device_memory(device=-1):

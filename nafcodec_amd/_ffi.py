@@ -134,6 +134,21 @@ class SummaryResult(Structure):
                 ("quality_total", c_uint64), ("ms", c_float)]
 
 
+class SearchOpts(Structure):
+    """nafgpu_search_opts: alphabet 0 = nucleotide (IUPAC sets), 1 = bytes (exact)."""
+    _fields_ = [("alphabet", c_uint8), ("both_strands", c_uint8), ("max_mismatches", c_uint8), ("reserved", c_uint8 * 5), ("max_hits", c_uint64)]
+
+
+class HitInfo(Structure):
+    """nafgpu_hit_info: which pattern a hit is of and with how many substitutions."""
+    _fields_ = [("pattern", c_uint32), ("mismatches", c_uint8), ("reserved", c_uint8 * 3)]
+
+
+class SearchResult(Structure):
+    _fields_ = [("d_regions", c_void_p), ("d_info", c_void_p), ("d_record_hit_begin", c_void_p),
+                ("n_hits", c_uint64), ("n_records", c_uint64), ("n_bases", c_uint64), ("pattern_hits", c_uint64 * 16), ("ms", c_float)]
+
+
 READ_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, POINTER(c_uint8), c_uint64)
 SEEK_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, c_int64, c_int)
 
@@ -155,6 +170,7 @@ EXPORTS = [
     "nafgpu_select", "nafgpu_find_records", "nafgpu_selection_format", "nafgpu_selection_copy_to_host", "nafgpu_selection_hash64",
     "nafgpu_selection_free",
     "nafgpu_summarize", "nafgpu_summarize_decoder", "nafgpu_summary_copy_to_host", "nafgpu_summary_free",
+    "nafgpu_search", "nafgpu_search_decoder", "nafgpu_hits_copy_to_host", "nafgpu_hits_free",
 ]
 
 
@@ -259,6 +275,14 @@ class Library:
             L.nafgpu_summary_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
             L.nafgpu_summary_free.argtypes = [c_void_p]
             L.nafgpu_summary_free.restype = None
+        if hasattr(L, "nafgpu_search"):                      # (absent from older builds loaded for A/B runs)
+            L.nafgpu_search.argtypes = [POINTER(EncodeSource), c_char_p, c_uint64, c_uint64, POINTER(SearchOpts), c_int, POINTER(c_void_p),
+                                        POINTER(SearchResult), POINTER(Error)]
+            L.nafgpu_search_decoder.argtypes = [c_void_p, c_char_p, c_uint64, c_uint64, POINTER(SearchOpts), POINTER(c_void_p), POINTER(SearchResult),
+                                                POINTER(Error)]
+            L.nafgpu_hits_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
+            L.nafgpu_hits_free.argtypes = [c_void_p]
+            L.nafgpu_hits_free.restype = None
 
     # ---- helpers ---------------------------------------------------------------------------
     def zstd_decompress(self, payload: bytes, size: int, device: int = -1) -> bytes:

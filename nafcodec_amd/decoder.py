@@ -319,7 +319,14 @@ class Decoder:
         (record, start, end) with end=None for the record's length, or (record, start, end, "-") for the reverse strand
         (reversed and complemented; "+" is the forward one); `record` may be a name (str / bytes), resolved through find():
         KeyError when no record has it.  name_regions: every id becomes id:START-END (1-based, inclusive) and id:START-END/rc.
-        ValueError for what the rules refuse."""
+        Instead of a list, `regions` may be the Hits of search() or any buffer of whole nafgpu_region structs (32 bytes each:
+        bytes, a memoryview, a numpy array of dtype nafcodec_amd.search.REGION): it goes to the library as it is, without a
+        Python object per region.  A buffer counts as such when its items are bytes or of 32 bytes; an array of integers is
+        a list of records like any other.  ValueError for what the rules refuse."""
+        packed = self._packed_regions(regions)
+        if packed is not None:
+            arr, n = packed
+            return self._select(arr, n, name_regions)
         regions = [r if isinstance(r, (tuple, list)) else (r, 0, None) for r in regions]
         named = sorted({r[0] for r in regions if isinstance(r[0], (str, bytes))}, key=repr)
         index = dict(zip(named, self.find(named))) if named else {}
@@ -337,9 +344,35 @@ class Decoder:
             arr[k].record, arr[k].start = int(record), int(r[1])
             arr[k].end = _ffi.REGION_END if r[2] is None else int(r[2])
             arr[k].reverse_complement = int(len(r) == 4 and r[3] == "-")
+        return self._select(arr, len(regions), name_regions)
+
+    @staticmethod
+    def _packed_regions(regions):
+        """-> (pointer to nafgpu_region, their number) when `regions` is a Hits or a buffer of whole structs, else None"""
+        from .search import Hits
+        if isinstance(regions, Hits):
+            regions = regions.regions()
+        elif isinstance(regions, (list, tuple, str)):
+            return None
+        try:
+            view = memoryview(regions)
+        except TypeError:
+            return None
+        size = ctypes.sizeof(_ffi.Region)
+        if view.itemsize not in (1, size):                   # an array of numbers (numpy.flatnonzero(...)) is a list of records, as ever
+            return None
+        if not view.c_contiguous or view.nbytes % size:
+            raise ValueError("a buffer of regions holds whole nafgpu_region structs of %d bytes, contiguous: %d bytes given" % (size, view.nbytes))
+        if view.nbytes and not view.readonly:
+            raw = (ctypes.c_uint8 * view.nbytes).from_buffer(view)
+        else:                                                # a read-only buffer (bytes) has no address ctypes may take: one copy
+            raw = (ctypes.c_uint8 * max(view.nbytes, 1)).from_buffer_copy(view.tobytes() or b"\0")
+        return ctypes.cast(raw, ctypes.POINTER(_ffi.Region)), view.nbytes // size
+
+    def _select(self, arr, n, name_regions):
         opts = _ffi.SelectOpts(name_regions=int(bool(name_regions)))
         h, res, err = c_void_p(), _ffi.SelectResult(), _ffi.Error()
-        rc = self._lib.c.nafgpu_select(self._h, arr, len(regions), byref(opts), byref(h), byref(res), byref(err))
+        rc = self._lib.c.nafgpu_select(self._h, arr, n, byref(opts), byref(h), byref(res), byref(err))
         if rc != _ffi.OK:
             self._raise_select(rc, err)
         return Selection(self._lib, h, res)
@@ -349,6 +382,14 @@ class Decoder:
         (decodes first if nothing is decoded yet) -> a Summary.  `classes`: 256 bytes, see nafcodec_amd.summary."""
         from .summary import _summarize_decoder
         return _summarize_decoder(self, classes)
+
+    def search(self, patterns, *, max_mismatches=0, both_strands=None, alphabet=None, max_hits=0):
+        """Where `patterns` (str or bytes, up to 16 of up to 64 letters) occur in the decoded records, matched on the GPU
+        (decodes first if nothing is decoded yet) -> Hits, whose regions select() takes.  alphabet None: by the archive
+        (dna and rna as nucleotides with IUPAC sets, protein and text as bytes); both_strands None: on for nucleotides;
+        max_mismatches: 0 .. 3 substitutions.  See nafcodec_amd.search."""
+        from .search import _search_decoder
+        return _search_decoder(self, patterns, max_mismatches, both_strands, alphabet, max_hits)
 
 
 class Selection:
@@ -403,6 +444,13 @@ class Selection:
         from .summary import summarize
         self._handle()
         return summarize(self, classes, device=device, _lib=self._lib)
+
+    def search(self, patterns, *, max_mismatches=0, both_strands=None, alphabet=None, max_hits=0, device=None):
+        """Where `patterns` occur in the selected records -> Hits (nafcodec_amd.search)."""
+        from .search import search
+        self._handle()
+        return search(self, patterns, max_mismatches=max_mismatches, both_strands=both_strands, alphabet=alphabet, max_hits=max_hits, device=device,
+                      _lib=self._lib)
 
     def close(self):
         if self._h is not None:

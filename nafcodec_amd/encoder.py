@@ -217,6 +217,13 @@ class ParsedText:
         self._handle()
         return summarize(self, classes, device=device, _lib=self._lib)
 
+    def search(self, patterns, *, max_mismatches=0, both_strands=None, alphabet=None, max_hits=0, device=None):
+        """Where `patterns` occur in the parsed records -> Hits (nafcodec_amd.search)."""
+        from .search import search
+        self._handle()
+        return search(self, patterns, max_mismatches=max_mismatches, both_strands=both_strands, alphabet=alphabet, max_hits=max_hits, device=device,
+                      _lib=self._lib)
+
     def close(self):
         if self._h is not None:
             h, self._h = self._h, None
