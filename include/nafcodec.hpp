@@ -204,6 +204,79 @@ private:
     size_t n_patterns_ = 0;
 };
 
+// (no counterpart in the reference) which records that are in HBM have equal sequences, found on the GPU: nafgpu_group has the
+// rules.  GroupOptions: alphabet -1 = by the archive for Decoder::group (nucleotide for dna and rna, bytes for protein and
+// text) and nucleotide elsewhere.
+struct GroupOptions {
+    int alphabet = -1;               // 0 nucleotide (4-bit codes: case and T/U ignored), 1 bytes (exact)
+    bool both_strands = false;       // nucleotide only: a record also equals its reverse complement
+};
+// What group returns: a Groups owns its device buffers and outlives its source; the accessors copy a table to the host.
+// Move-only.
+class Groups {
+public:
+    Groups(Groups &&o) noexcept : g_(std::exchange(o.g_, nullptr)), res_(o.res_) {}
+    Groups &operator=(Groups &&o) noexcept {
+        if (this != &o) {
+            nafgpu_groups_free(g_);
+            g_ = std::exchange(o.g_, nullptr);
+            res_ = o.res_;
+        }
+        return *this;
+    }
+    Groups(const Groups &) = delete;
+    ~Groups() { nafgpu_groups_free(g_); }
+
+    const nafgpu_group_result &result() const { return res_; }
+    uint64_t n_records() const { return res_.n_records; }
+    uint64_t n_groups() const { return res_.n_groups; }
+    uint64_t n_duplicates() const { return res_.n_records - res_.n_groups; }
+    uint64_t largest_group() const { return res_.largest_group; }
+    uint32_t rounds() const { return res_.rounds; }
+    float ms() const { return res_.ms; }
+    std::vector<uint64_t> representative() const { return table(res_.d_representative, res_.n_records); }   // the lowest record with an equal sequence
+    std::vector<uint64_t> group_of() const { return table(res_.d_group_of, res_.n_records); }
+    std::vector<uint8_t> strand() const { return table(res_.d_strand, res_.n_records); }                    // empty without both_strands
+    std::vector<uint64_t> group_first() const { return table(res_.d_group_first, res_.n_groups); }         // the representatives, ascending
+    std::vector<uint64_t> group_size() const { return table(res_.d_group_size, res_.n_groups); }
+
+    // dec null: `src` is grouped; else the decoder (it decodes first if nothing is decoded yet)
+    static Groups of(nafgpu_decoder *dec, const nafgpu_encode_source *src, const GroupOptions &opts, int device) {
+        nafgpu_group_opts o{};
+        bool nucleotide = opts.alphabet != 1;
+        if (dec && opts.alphabet < 0) {
+            nafgpu_header h;
+            nafgpu_get_header(dec, &h);
+            nucleotide = h.sequence_type <= 1;
+        }
+        o.alphabet = nucleotide ? 0 : 1;
+        o.both_strands = opts.both_strands ? 1 : 0;
+        nafgpu_groups *g = nullptr;
+        nafgpu_group_result r;
+        nafgpu_error e{};
+        const int rc = dec ? nafgpu_group_decoder(dec, &o, &g, &r, &e) : nafgpu_group(src, &o, device, &g, &r, &e);
+        if (rc != NAFGPU_OK) throw Error(e);
+        return Groups(g, r);
+    }
+
+private:
+    Groups(nafgpu_groups *g, const nafgpu_group_result &r) : g_(g), res_(r) {}
+    template <class T>
+    std::vector<T> table(const T *d_ptr, uint64_t n) const {
+        std::vector<T> out(d_ptr ? static_cast<size_t>(n) : 0);
+        const int rc = out.empty() ? NAFGPU_OK : nafgpu_groups_copy_to_host(g_, d_ptr, sizeof(T) * n, out.data());
+        if (rc != NAFGPU_OK) {
+            nafgpu_error e{};
+            e.status = rc;
+            std::snprintf(e.message, sizeof e.message, "nafgpu_groups_copy_to_host: %s", rc == NAFGPU_E_DEVICE ? "the copy failed" : "a null argument");
+            throw Error(e);
+        }
+        return out;
+    }
+    nafgpu_groups *g_ = nullptr;
+    nafgpu_group_result res_{};
+};
+
 class Decoder {   // mod.rs:285-461
 public:
     Decoder(Decoder &&o) noexcept
@@ -324,6 +397,25 @@ public:
     }
     // (no counterpart in the reference) where `patterns` occur in the decoded records (decodes first if nothing is decoded yet)
     Hits search(const std::vector<std::string> &patterns, const SearchOptions &opts = SearchOptions()) { return Hits::of(d_, nullptr, patterns, opts, -1); }
+    // (no counterpart in the reference) the decoded records whose sequences are equal (decodes first if nothing is decoded yet)
+    Groups group(const GroupOptions &opts = GroupOptions()) { return Groups::of(d_, nullptr, opts, -1); }
+    // the first record of every sequence, whole and in order: the archive without its duplicates
+    Selection select(const Groups &groups, bool name_regions = false) {
+        const std::vector<uint64_t> first = groups.group_first();
+        std::vector<nafgpu_region> regions(first.size());
+        for (size_t k = 0; k < first.size(); k++) {
+            regions[k] = nafgpu_region{};
+            regions[k].record = first[k];
+            regions[k].end = NAFGPU_REGION_END;
+        }
+        nafgpu_select_opts o{};
+        o.name_regions = name_regions ? 1 : 0;
+        nafgpu_selection *s = nullptr;
+        nafgpu_select_result r;
+        nafgpu_error e{};
+        if (nafgpu_select(d_, regions.data(), regions.size(), &o, &s, &r, &e) != NAFGPU_OK) throw Error(e);
+        return Selection(s, r);
+    }
     nafgpu_decoder *raw() const { return d_; }
 
 private:
@@ -581,6 +673,9 @@ inline Hits search(const Selection &sel, const std::vector<std::string> &pattern
 inline Hits search(const nafgpu_encode_source &src, const std::vector<std::string> &patterns, const SearchOptions &opts = SearchOptions(), int device = -1) {
     return Hits::of(nullptr, &src, patterns, opts, device);
 }
+
+inline Groups group(const Selection &sel, const GroupOptions &opts = GroupOptions(), int device = -1) { return Groups::of(nullptr, &sel.source(), opts, device); }
+inline Groups group(const nafgpu_encode_source &src, const GroupOptions &opts = GroupOptions(), int device = -1) { return Groups::of(nullptr, &src, opts, device); }
 
 // (no counterpart in the reference: the library keeps device memory of closed decoders for the next one -- nafgpu.h)
 inline void trim_device_memory(int device = -1) { (void)nafgpu_trim_device_memory(device); }

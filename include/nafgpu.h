@@ -627,6 +627,64 @@ int nafgpu_search_decoder(nafgpu_decoder *dec, const uint8_t *patterns, uint64_t
 int nafgpu_hits_copy_to_host(nafgpu_hits *h, const void *d_ptr, uint64_t n, void *dst);
 void nafgpu_hits_free(nafgpu_hits *h);
 
+/* ---- records in HBM -> the groups of records whose sequences are equal: PCR duplicates in reads, dereplication of amplicons,
+ * identical contigs (records picked by being the FIRST of their sequence) ----
+ * Hashing, table and comparison run in HIP kernels (group.hip); no letter comes to the host, the answer is 16 or 17 bytes per
+ * record and 16 per group.  The reference has no counterpart.  Rules:
+ *   key       the key of record k is the letters [d_record_end[k-1], d_record_end[k]).  Qualities, ids and comments play no
+ *             part.  All empty records form one group.  Letters behind the last record end belong to no record.
+ *   alphabet  0, nucleotide: two letters are equal when both are IUPAC letters (ACGTURYKMSWBDHVN, either case) with the same
+ *             4-bit code, so case and T/U are ignored, as in nafgpu_search; otherwise only when they are the same byte ('-'
+ *             included: it equals only itself).
+ *             1, bytes: exact bytes; the soft mask distinguishes.
+ *   strands   with both_strands (alphabet 0 only) a record is also equal to one whose reverse complement it is; the complement
+ *             is nafgpu_select's (the code with its bits reversed; any other byte is itself).  d_strand[k] is 1 only when k
+ *             differs from its representative read forward: a record that is its own reverse complement has strand 0, and so
+ *             has every representative.
+ *   output    d_representative[k] is the LOWEST record index whose sequence equals k's (k itself if it is the first).  Groups
+ *             are numbered by ascending representative: d_group_first is ascending, d_group_size sums to n_records,
+ *             d_group_of[d_group_first[g]] == g.  n_records == 0: NAFGPU_OK, all counts 0.
+ *   exactness equal hashes settle nothing: every record is compared with its representative letter by letter on the device,
+ *             and records whose hashes collide are sorted out in further table rounds (`rounds`; 1 unless 64-bit hashes
+ *             collided).  All indices and positions are 64-bit, integer work only; the result is a function of the input
+ *             alone, whatever the schedule, and no hash value appears in it.
+ *   refusals  NAFGPU_E_INVALID_ARG: a NULL argument (src, opts, out, res); d_sequence == NULL; n_records > 0 with
+ *             d_record_end == NULL; an alphabet other than 0 and 1; both_strands with the bytes alphabet.
+ *             NAFGPU_E_INVALID_LENGTH: a record end below the one in front of it or beyond the section -- checked on the
+ *             device, the message names the LOWEST offending record, and no kernel reads outside the section or the end
+ *             table whatever the table holds.  NAFGPU_E_DEVICE: an allocation, copy or kernel failed.
+ *             nafgpu_group_decoder decodes first if nothing is decoded yet, makes the checks of nafgpu_format_device (shard,
+ *             tiled output, a section that failed), needs the Length section (else NAFGPU_E_INVALID_ARG, as nafgpu_select),
+ *             and returns NAFGPU_E_IO / NAFGPU_IO_UNEXPECTED_EOF for a record end beyond what was decoded; its error is also
+ *             kept for nafgpu_last_error.  With opts == NULL its alphabet comes from the archive's sequence type (nucleotide
+ *             for DNA and RNA, bytes for protein and text), one strand; an explicit alphabet 0 on a protein or text archive is
+ *             NAFGPU_E_INVALID_ARG.
+ *             On any error nothing is produced. */
+typedef struct {
+    uint8_t alphabet;            /* 0 = nucleotide (4-bit codes: case and T/U ignored), 1 = bytes (exact) */
+    uint8_t both_strands;        /* nucleotide only: a record also equals its reverse complement */
+    uint8_t reserved[6];
+} nafgpu_group_opts;
+typedef struct nafgpu_groups nafgpu_groups;            /* owns its device buffers, like nafgpu_hits; it outlives its source */
+typedef struct {
+    const uint64_t *d_representative;        /* n_records: the LOWEST record index whose sequence equals this one's (itself if first) */
+    const uint64_t *d_group_of;              /* n_records: index of the record's group */
+    const uint8_t *d_strand;                 /* n_records: 1 = equal to the representative only as its reverse complement; NULL without both_strands */
+    const uint64_t *d_group_first;           /* n_groups: the representatives, ascending */
+    const uint64_t *d_group_size;            /* n_groups */
+    uint64_t n_records, n_groups, n_bases, largest_group;
+    uint32_t rounds;                         /* table rounds run; 1 unless hashes collided */
+    float ms;                                /* first kernel to last, HIP events */
+} nafgpu_group_result;
+/* device -1 = current */
+int nafgpu_group(const nafgpu_encode_source *src, const nafgpu_group_opts *opts, int device, nafgpu_groups **out,
+                 nafgpu_group_result *res, nafgpu_error *err);
+int nafgpu_group_decoder(nafgpu_decoder *dec, const nafgpu_group_opts *opts, nafgpu_groups **out, nafgpu_group_result *res,
+                         nafgpu_error *err);
+/* n bytes from a pointer of the result; NAFGPU_E_INVALID_ARG: a NULL argument, NAFGPU_E_DEVICE: the copy failed */
+int nafgpu_groups_copy_to_host(nafgpu_groups *g, const void *d_ptr, uint64_t n, void *dst);
+void nafgpu_groups_free(nafgpu_groups *g);
+
 /* order-sensitive 64-bit checksum used for full-size parity checks: sum over the 8-byte words w_j of
  * mix64(w_j ^ (j + 1) * K) -- every word is mixed non-linearly with its position before it is added, so
  * byte errors cannot cancel -- see hash64.h */

@@ -149,6 +149,17 @@ class SearchResult(Structure):
                 ("n_hits", c_uint64), ("n_records", c_uint64), ("n_bases", c_uint64), ("pattern_hits", c_uint64 * 16), ("ms", c_float)]
 
 
+class GroupOpts(Structure):
+    """nafgpu_group_opts: alphabet 0 = nucleotide (4-bit codes), 1 = bytes (exact)."""
+    _fields_ = [("alphabet", c_uint8), ("both_strands", c_uint8), ("reserved", c_uint8 * 6)]
+
+
+class GroupResult(Structure):
+    _fields_ = [("d_representative", c_void_p), ("d_group_of", c_void_p), ("d_strand", c_void_p), ("d_group_first", c_void_p),
+                ("d_group_size", c_void_p), ("n_records", c_uint64), ("n_groups", c_uint64), ("n_bases", c_uint64),
+                ("largest_group", c_uint64), ("rounds", c_uint32), ("ms", c_float)]
+
+
 READ_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, POINTER(c_uint8), c_uint64)
 SEEK_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, c_int64, c_int)
 
@@ -171,6 +182,7 @@ EXPORTS = [
     "nafgpu_selection_free",
     "nafgpu_summarize", "nafgpu_summarize_decoder", "nafgpu_summary_copy_to_host", "nafgpu_summary_free",
     "nafgpu_search", "nafgpu_search_decoder", "nafgpu_hits_copy_to_host", "nafgpu_hits_free",
+    "nafgpu_group", "nafgpu_group_decoder", "nafgpu_groups_copy_to_host", "nafgpu_groups_free",
 ]
 
 
@@ -283,6 +295,12 @@ class Library:
             L.nafgpu_hits_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
             L.nafgpu_hits_free.argtypes = [c_void_p]
             L.nafgpu_hits_free.restype = None
+        if hasattr(L, "nafgpu_group"):                       # (absent from older builds loaded for A/B runs)
+            L.nafgpu_group.argtypes = [POINTER(EncodeSource), POINTER(GroupOpts), c_int, POINTER(c_void_p), POINTER(GroupResult), POINTER(Error)]
+            L.nafgpu_group_decoder.argtypes = [c_void_p, POINTER(GroupOpts), POINTER(c_void_p), POINTER(GroupResult), POINTER(Error)]
+            L.nafgpu_groups_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
+            L.nafgpu_groups_free.argtypes = [c_void_p]
+            L.nafgpu_groups_free.restype = None
 
     # ---- helpers ---------------------------------------------------------------------------
     def zstd_decompress(self, payload: bytes, size: int, device: int = -1) -> bytes:

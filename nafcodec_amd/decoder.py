@@ -322,7 +322,11 @@ class Decoder:
         Instead of a list, `regions` may be the Hits of search() or any buffer of whole nafgpu_region structs (32 bytes each:
         bytes, a memoryview, a numpy array of dtype nafcodec_amd.search.REGION): it goes to the library as it is, without a
         Python object per region.  A buffer counts as such when its items are bytes or of 32 bytes; an array of integers is
-        a list of records like any other.  ValueError for what the rules refuse."""
+        a list of records like any other.  The Groups of group() stand for their representatives as whole records, in
+        order: the first record of every sequence.  ValueError for what the rules refuse."""
+        from .group import Groups
+        if isinstance(regions, Groups):
+            regions = regions._regions()
         packed = self._packed_regions(regions)
         if packed is not None:
             arr, n = packed
@@ -391,6 +395,14 @@ class Decoder:
         from .search import _search_decoder
         return _search_decoder(self, patterns, max_mismatches, both_strands, alphabet, max_hits)
 
+    def group(self, *, both_strands=False, alphabet=None):
+        """The decoded records whose sequences are equal, found on the GPU (decodes first if nothing is decoded yet) ->
+        Groups, which select() takes: the first record of every sequence.  alphabet None: by the archive (dna and rna by
+        their 4-bit codes, so case and T/U are ignored; protein and text as bytes); both_strands: a record also equals its
+        reverse complement.  See nafcodec_amd.group."""
+        from .group import _group_decoder
+        return _group_decoder(self, both_strands, alphabet)
+
 
 class Selection:
     """What Decoder.select() returns: records cut out of a decoded archive, in HBM, with the fields encode_device() reads
@@ -451,6 +463,12 @@ class Selection:
         self._handle()
         return search(self, patterns, max_mismatches=max_mismatches, both_strands=both_strands, alphabet=alphabet, max_hits=max_hits, device=device,
                       _lib=self._lib)
+
+    def group(self, *, both_strands=False, alphabet=None, device=None):
+        """The selected records whose sequences are equal -> Groups (nafcodec_amd.group)."""
+        from .group import group
+        self._handle()
+        return group(self, both_strands=both_strands, alphabet=alphabet, device=device, _lib=self._lib)
 
     def close(self):
         if self._h is not None:

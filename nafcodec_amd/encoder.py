@@ -224,6 +224,12 @@ class ParsedText:
         return search(self, patterns, max_mismatches=max_mismatches, both_strands=both_strands, alphabet=alphabet, max_hits=max_hits, device=device,
                       _lib=self._lib)
 
+    def group(self, *, both_strands=False, alphabet=None, device=None):
+        """The parsed records whose sequences are equal -> Groups (nafcodec_amd.group)."""
+        from .group import group
+        self._handle()
+        return group(self, both_strands=both_strands, alphabet=alphabet, device=device, _lib=self._lib)
+
     def close(self):
         if self._h is not None:
             h, self._h = self._h, None
