@@ -277,6 +277,81 @@ private:
     nafgpu_group_result res_{};
 };
 
+// (no counterpart in the reference) the window of every record that quality trimming keeps, found on the GPU: nafgpu_trim has
+// the rules.  0 turns a step off.
+struct TrimOptions {
+    unsigned cut_front = 0, cut_tail = 0;   // step 1: the running-sum cutoffs of `cutadapt -q FRONT,TAIL`
+    unsigned window = 0, window_quality = 0;   // step 2: the first window of W (1 .. 64) values whose mean is below Q
+    bool trim_n = false;             // step 3: N at either end
+    uint64_t min_length = 0;         // step 4: a record whose window is shorter is not kept
+    bool interleaved = false;        //         records 2j and 2j + 1 are mates: both are kept only when both pass
+    unsigned quality_base = 33;
+};
+// What trim returns: a Trims owns its device buffers and outlives its source; the accessors copy a table to the host.
+// Move-only.
+class Trims {
+public:
+    Trims(Trims &&o) noexcept : t_(std::exchange(o.t_, nullptr)), res_(o.res_) {}
+    Trims &operator=(Trims &&o) noexcept {
+        if (this != &o) {
+            nafgpu_trims_free(t_);
+            t_ = std::exchange(o.t_, nullptr);
+            res_ = o.res_;
+        }
+        return *this;
+    }
+    Trims(const Trims &) = delete;
+    ~Trims() { nafgpu_trims_free(t_); }
+
+    const nafgpu_trim_result &result() const { return res_; }
+    uint64_t n_records() const { return res_.n_records; }
+    uint64_t n_kept() const { return res_.n_kept; }
+    uint64_t n_changed() const { return res_.n_changed; }
+    uint64_t bases_in_windows() const { return res_.bases_in_windows; }
+    uint64_t bases_kept() const { return res_.bases_kept; }
+    float ms() const { return res_.ms; }
+    std::vector<nafgpu_region> regions() const { return table(res_.d_regions, res_.n_records); }            // {k, a, b, 0} per record
+    std::vector<uint8_t> keep() const { return table(res_.d_keep, res_.n_records); }
+    std::vector<nafgpu_region> kept_regions() const { return table(res_.d_kept_regions, res_.n_kept); }     // ready for nafgpu_select
+
+    // dec null: `src` is trimmed; else the decoder (it decodes first if nothing is decoded yet)
+    static Trims of(nafgpu_decoder *dec, const nafgpu_encode_source *src, const TrimOptions &opts, int device) {
+        nafgpu_trim_opts o{};
+        auto byte = [](unsigned v) { return static_cast<uint8_t>(v > 255 ? 255 : v); };
+        o.quality_base = byte(opts.quality_base);
+        o.cut_front = byte(opts.cut_front);
+        o.cut_tail = byte(opts.cut_tail);
+        o.window = byte(opts.window);
+        o.window_quality = byte(opts.window_quality);
+        o.trim_n = opts.trim_n ? 1 : 0;
+        o.interleaved = opts.interleaved ? 1 : 0;
+        o.min_length = opts.min_length;
+        nafgpu_trims *t = nullptr;
+        nafgpu_trim_result r;
+        nafgpu_error e{};
+        const int rc = dec ? nafgpu_trim_decoder(dec, &o, &t, &r, &e) : nafgpu_trim(src, &o, device, &t, &r, &e);
+        if (rc != NAFGPU_OK) throw Error(e);
+        return Trims(t, r);
+    }
+
+private:
+    Trims(nafgpu_trims *t, const nafgpu_trim_result &r) : t_(t), res_(r) {}
+    template <class T>
+    std::vector<T> table(const T *d_ptr, uint64_t n) const {
+        std::vector<T> out(d_ptr ? static_cast<size_t>(n) : 0);
+        const int rc = out.empty() ? NAFGPU_OK : nafgpu_trims_copy_to_host(t_, d_ptr, sizeof(T) * n, out.data());
+        if (rc != NAFGPU_OK) {
+            nafgpu_error e{};
+            e.status = rc;
+            std::snprintf(e.message, sizeof e.message, "nafgpu_trims_copy_to_host: %s", rc == NAFGPU_E_DEVICE ? "the copy failed" : "a null argument");
+            throw Error(e);
+        }
+        return out;
+    }
+    nafgpu_trims *t_ = nullptr;
+    nafgpu_trim_result res_{};
+};
+
 class Decoder {   // mod.rs:285-461
 public:
     Decoder(Decoder &&o) noexcept
@@ -387,6 +462,20 @@ public:
     // pattern is written
     Selection select(const Hits &hits, bool name_regions = false) {
         const std::vector<nafgpu_region> regions = hits.regions();
+        nafgpu_select_opts o{};
+        o.name_regions = name_regions ? 1 : 0;
+        nafgpu_selection *s = nullptr;
+        nafgpu_select_result r;
+        nafgpu_error e{};
+        if (nafgpu_select(d_, regions.data(), regions.size(), &o, &s, &r, &e) != NAFGPU_OK) throw Error(e);
+        return Selection(s, r);
+    }
+    // (no counterpart in the reference) the window of every decoded record that quality trimming keeps (decodes first if nothing
+    // is decoded yet)
+    Trims trim(const TrimOptions &opts = TrimOptions()) { return Trims::of(d_, nullptr, opts, -1); }
+    // the kept records cut to their windows, in order
+    Selection select(const Trims &trims, bool name_regions = false) {
+        const std::vector<nafgpu_region> regions = trims.kept_regions();
         nafgpu_select_opts o{};
         o.name_regions = name_regions ? 1 : 0;
         nafgpu_selection *s = nullptr;
@@ -676,6 +765,9 @@ inline Hits search(const nafgpu_encode_source &src, const std::vector<std::strin
 
 inline Groups group(const Selection &sel, const GroupOptions &opts = GroupOptions(), int device = -1) { return Groups::of(nullptr, &sel.source(), opts, device); }
 inline Groups group(const nafgpu_encode_source &src, const GroupOptions &opts = GroupOptions(), int device = -1) { return Groups::of(nullptr, &src, opts, device); }
+// the trims of a selection index the selection's records
+inline Trims trim(const Selection &sel, const TrimOptions &opts = TrimOptions(), int device = -1) { return Trims::of(nullptr, &sel.source(), opts, device); }
+inline Trims trim(const nafgpu_encode_source &src, const TrimOptions &opts = TrimOptions(), int device = -1) { return Trims::of(nullptr, &src, opts, device); }
 
 // (no counterpart in the reference: the library keeps device memory of closed decoders for the next one -- nafgpu.h)
 inline void trim_device_memory(int device = -1) { (void)nafgpu_trim_device_memory(device); }

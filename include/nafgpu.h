@@ -685,6 +685,74 @@ int nafgpu_group_decoder(nafgpu_decoder *dec, const nafgpu_group_opts *opts, naf
 int nafgpu_groups_copy_to_host(nafgpu_groups *g, const void *d_ptr, uint64_t n, void *dst);
 void nafgpu_groups_free(nafgpu_groups *g);
 
+/* ---- records in HBM -> the window of every record that quality trimming keeps, as regions for nafgpu_select (records CUT where
+ * a read goes bad: the running-sum rule of `cutadapt -q` and `bwa -q`, a sliding window, N ends, a length filter) ----
+ * The trimming runs in HIP kernels (trim.hip); letters and qualities stay in HBM, the answer is 33 bytes per record.  The
+ * reference has no counterpart.  Rules:
+ *   records   record k is positions [d_record_end[k-1], d_record_end[k]) of the sections, of length L; its letters are
+ *             s[0..L), its quality values v[i] = (int) q[i] - quality_base, signed, so a byte below the base is negative.
+ *             d_record_end == NULL or n_records == 0: the whole section is record 0 (n_records of the result is 1), as in
+ *             nafgpu_search.  Letters behind the last record end belong to no record.  The window starts as [a, b) = [0, L);
+ *             the steps run in this order, each on what the one before left.
+ *   1 sums    cut_front, cut_tail; 0 turns an end off.  The rule `cutadapt -q FRONT,TAIL` and `bwa -q` state, both ends on
+ *             the whole record, independently.  Front: sum = 0, best = 0, a = 0; for i = 0 .. L-1: sum += cut_front - v[i];
+ *             stop if sum < 0; if sum > best then best = sum, a = i + 1.  Tail: the mirror image from i = L-1 downward with
+ *             cut_tail; sum > best sets b = i.  Ties keep the shorter cut (the comparison is strict).  a >= b: the window is
+ *             empty.  Sums are 64-bit signed; a record may be longer than 2^32.
+ *   2 window  window = W in 1 .. 64, window_quality = Q; W = 0 turns it off.  The lowest i with a <= i, i + W <= b and
+ *             v[i] + .. + v[i+W-1] < W * Q becomes b.  Without such a window (b - a < W is one such case) nothing changes.
+ *             This is the cut point of the 5'-to-3' window trimmers (Trimmomatic SLIDINGWINDOW, fastp --cut_right) WITHOUT
+ *             their clean-up afterwards: the output of those tools may differ by the few letters they drop or keep around
+ *             that point.
+ *   3 N ends  trim_n: a advances while a < b and s[a] is N or n; b retreats likewise.  An N in the middle stays.
+ *   4 form    an empty window is written as a = b = 0.  keep = (b - a >= min_length); with min_length == 0 every record is
+ *             kept, empty ones included.  With `interleaved` records 2j and 2j+1 are mates: both are kept only when both pass.
+ *   output    d_regions[k] = {k, a, b, 0} for every record; d_keep[k]; d_kept_regions: the regions of the kept records in
+ *             ascending order, n_kept of them, compacted on the device, ready for nafgpu_select once copied to the host.
+ *             n_changed: records whose window is not [0, L); bases_in_windows: the sum of b - a over all records;
+ *             bases_kept: the same sum over the kept records.  Integer work only: the result is a function of the input
+ *             alone, whatever the schedule.
+ *   refusals  NAFGPU_E_INVALID_ARG: a NULL argument, opts included; both sections NULL; a quality step (cut_front, cut_tail,
+ *             window) without d_quality; trim_n without d_sequence; window > 64; interleaved with an odd number of records.
+ *             NAFGPU_E_INVALID_LENGTH: both sections given and n_quality != n_bases; a record end below the one in front of
+ *             it or beyond the section -- checked on the device, the message names the LOWEST offending record, and no
+ *             kernel reads outside a section or the end table whatever the table holds.  NAFGPU_E_DEVICE: an allocation,
+ *             copy or kernel failed.  All options off is allowed: every region is then the whole record.
+ *             nafgpu_trim_decoder decodes first if nothing is decoded yet, makes the checks of nafgpu_format_device (shard,
+ *             tiled output, a section that failed), needs the Length section (else NAFGPU_E_INVALID_ARG, as nafgpu_select),
+ *             and returns NAFGPU_E_IO / NAFGPU_IO_UNEXPECTED_EOF for a record end beyond what was decoded; a quality step on
+ *             an archive without a Quality section is NAFGPU_E_INVALID_ARG; its error is also kept for nafgpu_last_error.
+ *             On any error nothing is produced. */
+#define NAFGPU_TRIM_MAX_WINDOW 64
+typedef struct {
+    uint8_t quality_base;        /* what a quality byte of value 0 is written as: 33 for today's FASTQ (used as given) */
+    uint8_t cut_front, cut_tail; /* step 1: the cutoffs of the running sums; 0 = that end is not cut */
+    uint8_t window;              /* step 2: W, 1 .. 64; 0 = off */
+    uint8_t window_quality;      /* step 2: Q, a window fails when its mean is below it */
+    uint8_t trim_n;              /* step 3 */
+    uint8_t interleaved;         /* step 4: records 2j and 2j+1 are mates */
+    uint8_t reserved;
+    uint64_t min_length;         /* step 4: a record whose window is shorter is not kept */
+} nafgpu_trim_opts;
+typedef struct nafgpu_trims nafgpu_trims;              /* owns its device buffers, like nafgpu_hits; it outlives its source */
+typedef struct {
+    const nafgpu_region *d_regions;          /* n_records: {k, a, b, 0} */
+    const uint8_t *d_keep;                   /* n_records: 1 = kept */
+    const nafgpu_region *d_kept_regions;     /* n_kept: the regions of the kept records, ascending */
+    uint64_t n_records, n_kept, n_bases;
+    uint64_t n_changed;                      /* records whose window is not [0, L) */
+    uint64_t bases_in_windows, bases_kept;
+    float ms;                                /* the trim kernels, HIP events */
+} nafgpu_trim_result;
+/* device -1 = current */
+int nafgpu_trim(const nafgpu_encode_source *src, const nafgpu_trim_opts *opts, int device, nafgpu_trims **out,
+                nafgpu_trim_result *res, nafgpu_error *err);
+int nafgpu_trim_decoder(nafgpu_decoder *dec, const nafgpu_trim_opts *opts, nafgpu_trims **out, nafgpu_trim_result *res,
+                        nafgpu_error *err);
+/* n bytes from a pointer of the result; NAFGPU_E_INVALID_ARG: a NULL argument, NAFGPU_E_DEVICE: the copy failed */
+int nafgpu_trims_copy_to_host(nafgpu_trims *t, const void *d_ptr, uint64_t n, void *dst);
+void nafgpu_trims_free(nafgpu_trims *t);
+
 /* order-sensitive 64-bit checksum used for full-size parity checks: sum over the 8-byte words w_j of
  * mix64(w_j ^ (j + 1) * K) -- every word is mixed non-linearly with its position before it is added, so
  * byte errors cannot cancel -- see hash64.h */

@@ -160,6 +160,17 @@ class GroupResult(Structure):
                 ("largest_group", c_uint64), ("rounds", c_uint32), ("ms", c_float)]
 
 
+class TrimOpts(Structure):
+    """nafgpu_trim_opts: the four steps of nafgpu_trim; 0 turns a step off."""
+    _fields_ = [("quality_base", c_uint8), ("cut_front", c_uint8), ("cut_tail", c_uint8), ("window", c_uint8), ("window_quality", c_uint8),
+                ("trim_n", c_uint8), ("interleaved", c_uint8), ("reserved", c_uint8), ("min_length", c_uint64)]
+
+
+class TrimResult(Structure):
+    _fields_ = [("d_regions", c_void_p), ("d_keep", c_void_p), ("d_kept_regions", c_void_p), ("n_records", c_uint64), ("n_kept", c_uint64),
+                ("n_bases", c_uint64), ("n_changed", c_uint64), ("bases_in_windows", c_uint64), ("bases_kept", c_uint64), ("ms", c_float)]
+
+
 READ_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, POINTER(c_uint8), c_uint64)
 SEEK_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, c_int64, c_int)
 
@@ -183,6 +194,7 @@ EXPORTS = [
     "nafgpu_summarize", "nafgpu_summarize_decoder", "nafgpu_summary_copy_to_host", "nafgpu_summary_free",
     "nafgpu_search", "nafgpu_search_decoder", "nafgpu_hits_copy_to_host", "nafgpu_hits_free",
     "nafgpu_group", "nafgpu_group_decoder", "nafgpu_groups_copy_to_host", "nafgpu_groups_free",
+    "nafgpu_trim", "nafgpu_trim_decoder", "nafgpu_trims_copy_to_host", "nafgpu_trims_free",
 ]
 
 
@@ -301,6 +313,12 @@ class Library:
             L.nafgpu_groups_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
             L.nafgpu_groups_free.argtypes = [c_void_p]
             L.nafgpu_groups_free.restype = None
+        if hasattr(L, "nafgpu_trim"):                        # (absent from older builds loaded for A/B runs)
+            L.nafgpu_trim.argtypes = [POINTER(EncodeSource), POINTER(TrimOpts), c_int, POINTER(c_void_p), POINTER(TrimResult), POINTER(Error)]
+            L.nafgpu_trim_decoder.argtypes = [c_void_p, POINTER(TrimOpts), POINTER(c_void_p), POINTER(TrimResult), POINTER(Error)]
+            L.nafgpu_trims_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
+            L.nafgpu_trims_free.argtypes = [c_void_p]
+            L.nafgpu_trims_free.restype = None
 
     # ---- helpers ---------------------------------------------------------------------------
     def zstd_decompress(self, payload: bytes, size: int, device: int = -1) -> bytes:

@@ -323,10 +323,14 @@ class Decoder:
         bytes, a memoryview, a numpy array of dtype nafcodec_amd.search.REGION): it goes to the library as it is, without a
         Python object per region.  A buffer counts as such when its items are bytes or of 32 bytes; an array of integers is
         a list of records like any other.  The Groups of group() stand for their representatives as whole records, in
-        order: the first record of every sequence.  ValueError for what the rules refuse."""
+        order: the first record of every sequence.  The Trims of trim() stand for their kept regions: every kept record cut
+        to its window.  ValueError for what the rules refuse."""
         from .group import Groups
+        from .trim import Trims
         if isinstance(regions, Groups):
             regions = regions._regions()
+        elif isinstance(regions, Trims):
+            regions = regions.kept_regions()
         packed = self._packed_regions(regions)
         if packed is not None:
             arr, n = packed
@@ -403,6 +407,14 @@ class Decoder:
         from .group import _group_decoder
         return _group_decoder(self, both_strands, alphabet)
 
+    def trim(self, *, cut_front=0, cut_tail=0, window=None, trim_n=False, min_length=0, interleaved=False, quality_base=33):
+        """The window of every decoded record that quality trimming keeps, found on the GPU (decodes first if nothing is
+        decoded yet) -> Trims, which select() takes: the kept records cut to their windows.  cut_front, cut_tail: the
+        running-sum cutoffs of `cutadapt -q`; window: (W, Q), the first window of W values whose mean is below Q; trim_n: N at
+        either end; min_length and interleaved: which records are kept.  See nafcodec_amd.trim."""
+        from .trim import _trim_decoder
+        return _trim_decoder(self, cut_front, cut_tail, window, trim_n, min_length, interleaved, quality_base)
+
 
 class Selection:
     """What Decoder.select() returns: records cut out of a decoded archive, in HBM, with the fields encode_device() reads
@@ -469,6 +481,14 @@ class Selection:
         from .group import group
         self._handle()
         return group(self, both_strands=both_strands, alphabet=alphabet, device=device, _lib=self._lib)
+
+    def trim(self, *, cut_front=0, cut_tail=0, window=None, trim_n=False, min_length=0, interleaved=False, quality_base=33, device=None):
+        """The window of every selected record that quality trimming keeps -> Trims (nafcodec_amd.trim); their records are
+        this selection's."""
+        from .trim import trim
+        self._handle()
+        return trim(self, cut_front=cut_front, cut_tail=cut_tail, window=window, trim_n=trim_n, min_length=min_length, interleaved=interleaved,
+                    quality_base=quality_base, device=device, _lib=self._lib)
 
     def close(self):
         if self._h is not None:

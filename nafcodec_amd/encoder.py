@@ -230,6 +230,13 @@ class ParsedText:
         self._handle()
         return group(self, both_strands=both_strands, alphabet=alphabet, device=device, _lib=self._lib)
 
+    def trim(self, *, cut_front=0, cut_tail=0, window=None, trim_n=False, min_length=0, interleaved=False, quality_base=33, device=None):
+        """The window of every parsed record that quality trimming keeps -> Trims (nafcodec_amd.trim)."""
+        from .trim import trim
+        self._handle()
+        return trim(self, cut_front=cut_front, cut_tail=cut_tail, window=window, trim_n=trim_n, min_length=min_length, interleaved=interleaved,
+                    quality_base=quality_base, device=device, _lib=self._lib)
+
     def close(self):
         if self._h is not None:
             h, self._h = self._h, None
