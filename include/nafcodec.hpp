@@ -352,6 +352,125 @@ private:
     nafgpu_trim_result res_{};
 };
 
+// (no counterpart in the reference) the k-mers of a reference as a set in HBM, and records screened against it:
+// nafgpu_kmers_build and nafgpu_screen have the rules.
+struct KmerOptions {
+    unsigned k = 31;                 // 1 .. 31
+    bool canonical = true;           // a k-mer and its reverse complement are one key
+};
+// What kmers returns: a KmerSet owns its table and outlives its source.  Move-only.
+class KmerSet {
+public:
+    KmerSet(KmerSet &&o) noexcept : k_(std::exchange(o.k_, nullptr)), res_(o.res_) {}
+    KmerSet &operator=(KmerSet &&o) noexcept {
+        if (this != &o) {
+            nafgpu_kmers_free(k_);
+            k_ = std::exchange(o.k_, nullptr);
+            res_ = o.res_;
+        }
+        return *this;
+    }
+    KmerSet(const KmerSet &) = delete;
+    ~KmerSet() { nafgpu_kmers_free(k_); }
+
+    const nafgpu_kmers_result &result() const { return res_; }
+    const nafgpu_kmers *raw() const { return k_; }
+    unsigned k() const { return res_.k; }
+    bool canonical() const { return res_.canonical != 0; }
+    uint64_t n_windows() const { return res_.n_windows; }
+    uint64_t n_kmers() const { return res_.n_kmers; }
+    uint64_t slots() const { return res_.slots; }
+    float ms() const { return res_.ms; }
+
+    // dec null: the k-mers of `src`; else the decoder's (it decodes first if nothing is decoded yet)
+    static KmerSet of(nafgpu_decoder *dec, const nafgpu_encode_source *src, const KmerOptions &opts, int device) {
+        nafgpu_kmer_opts o{};
+        o.k = static_cast<uint8_t>(opts.k > 255 ? 255 : opts.k);
+        o.canonical = opts.canonical ? 1 : 0;
+        nafgpu_kmers *k = nullptr;
+        nafgpu_kmers_result r;
+        nafgpu_error e{};
+        const int rc = dec ? nafgpu_kmers_build_decoder(dec, &o, &k, &r, &e) : nafgpu_kmers_build(src, &o, device, &k, &r, &e);
+        if (rc != NAFGPU_OK) throw Error(e);
+        return KmerSet(k, r);
+    }
+
+private:
+    KmerSet(nafgpu_kmers *k, const nafgpu_kmers_result &r) : k_(k), res_(r) {}
+    nafgpu_kmers *k_ = nullptr;
+    nafgpu_kmers_result res_{};
+};
+
+struct ScreenOptions {
+    uint64_t min_hits = 1;           // a record matches with at least so many windows in the set
+    unsigned min_percent = 0;        //   and so large a share of its windows, 0 .. 100
+    bool interleaved = false;        // records 2j and 2j + 1 are mates: both match when either does
+    bool keep_matched = false;       // false: what does not match is kept (decontamination); true: what matches (baiting)
+};
+// What screen returns: a Screens owns its device buffers and outlives its source and its set; the accessors copy a table to the
+// host.  Move-only.
+class Screens {
+public:
+    Screens(Screens &&o) noexcept : s_(std::exchange(o.s_, nullptr)), res_(o.res_) {}
+    Screens &operator=(Screens &&o) noexcept {
+        if (this != &o) {
+            nafgpu_screens_free(s_);
+            s_ = std::exchange(o.s_, nullptr);
+            res_ = o.res_;
+        }
+        return *this;
+    }
+    Screens(const Screens &) = delete;
+    ~Screens() { nafgpu_screens_free(s_); }
+
+    const nafgpu_screen_result &result() const { return res_; }
+    uint64_t n_records() const { return res_.n_records; }
+    uint64_t n_matched() const { return res_.n_matched; }
+    uint64_t n_kept() const { return res_.n_kept; }
+    uint64_t n_windows() const { return res_.n_windows; }
+    uint64_t n_hits() const { return res_.n_hits; }
+    uint64_t bases_kept() const { return res_.bases_kept; }
+    float ms() const { return res_.ms; }
+    std::vector<uint64_t> windows() const { return table(res_.d_windows, res_.n_records); }
+    std::vector<uint64_t> hits() const { return table(res_.d_hits, res_.n_records); }
+    std::vector<nafgpu_region> regions() const { return table(res_.d_regions, res_.n_records); }            // {r, a, b, 0} per record
+    std::vector<uint8_t> match() const { return table(res_.d_match, res_.n_records); }
+    std::vector<uint8_t> keep() const { return table(res_.d_keep, res_.n_records); }
+    std::vector<nafgpu_region> kept_regions() const { return table(res_.d_kept_regions, res_.n_kept); }     // ready for nafgpu_select
+
+    // dec null: `src` is screened; else the decoder (it decodes first if nothing is decoded yet)
+    static Screens of(nafgpu_decoder *dec, const nafgpu_encode_source *src, const KmerSet &set, const ScreenOptions &opts, int device) {
+        nafgpu_screen_opts o{};
+        o.keep_matched = opts.keep_matched ? 1 : 0;
+        o.interleaved = opts.interleaved ? 1 : 0;
+        o.min_percent = static_cast<uint8_t>(opts.min_percent > 255 ? 255 : opts.min_percent);
+        o.min_hits = opts.min_hits;
+        nafgpu_screens *s = nullptr;
+        nafgpu_screen_result r;
+        nafgpu_error e{};
+        const int rc = dec ? nafgpu_screen_decoder(dec, set.raw(), &o, &s, &r, &e) : nafgpu_screen(src, set.raw(), &o, device, &s, &r, &e);
+        if (rc != NAFGPU_OK) throw Error(e);
+        return Screens(s, r);
+    }
+
+private:
+    Screens(nafgpu_screens *s, const nafgpu_screen_result &r) : s_(s), res_(r) {}
+    template <class T>
+    std::vector<T> table(const T *d_ptr, uint64_t n) const {
+        std::vector<T> out(d_ptr ? static_cast<size_t>(n) : 0);
+        const int rc = out.empty() ? NAFGPU_OK : nafgpu_screens_copy_to_host(s_, d_ptr, sizeof(T) * n, out.data());
+        if (rc != NAFGPU_OK) {
+            nafgpu_error e{};
+            e.status = rc;
+            std::snprintf(e.message, sizeof e.message, "nafgpu_screens_copy_to_host: %s", rc == NAFGPU_E_DEVICE ? "the copy failed" : "a null argument");
+            throw Error(e);
+        }
+        return out;
+    }
+    nafgpu_screens *s_ = nullptr;
+    nafgpu_screen_result res_{};
+};
+
 class Decoder {   // mod.rs:285-461
 public:
     Decoder(Decoder &&o) noexcept
@@ -476,6 +595,21 @@ public:
     // the kept records cut to their windows, in order
     Selection select(const Trims &trims, bool name_regions = false) {
         const std::vector<nafgpu_region> regions = trims.kept_regions();
+        nafgpu_select_opts o{};
+        o.name_regions = name_regions ? 1 : 0;
+        nafgpu_selection *s = nullptr;
+        nafgpu_select_result r;
+        nafgpu_error e{};
+        if (nafgpu_select(d_, regions.data(), regions.size(), &o, &s, &r, &e) != NAFGPU_OK) throw Error(e);
+        return Selection(s, r);
+    }
+    // (no counterpart in the reference) the distinct k-mers of the decoded records as a set in HBM, and the decoded records
+    // against such a set (either decodes first if nothing is decoded yet)
+    KmerSet kmers(const KmerOptions &opts = KmerOptions()) { return KmerSet::of(d_, nullptr, opts, -1); }
+    Screens screen(const KmerSet &set, const ScreenOptions &opts = ScreenOptions()) { return Screens::of(d_, nullptr, set, opts, -1); }
+    // the kept records, whole and in order
+    Selection select(const Screens &screens, bool name_regions = false) {
+        const std::vector<nafgpu_region> regions = screens.kept_regions();
         nafgpu_select_opts o{};
         o.name_regions = name_regions ? 1 : 0;
         nafgpu_selection *s = nullptr;
@@ -768,6 +902,17 @@ inline Groups group(const nafgpu_encode_source &src, const GroupOptions &opts = 
 // the trims of a selection index the selection's records
 inline Trims trim(const Selection &sel, const TrimOptions &opts = TrimOptions(), int device = -1) { return Trims::of(nullptr, &sel.source(), opts, device); }
 inline Trims trim(const nafgpu_encode_source &src, const TrimOptions &opts = TrimOptions(), int device = -1) { return Trims::of(nullptr, &src, opts, device); }
+
+// the k-mers of a selection or a source, and a selection or a source against a set: the screens of a selection index the
+// selection's records
+inline KmerSet kmers(const Selection &sel, const KmerOptions &opts = KmerOptions(), int device = -1) { return KmerSet::of(nullptr, &sel.source(), opts, device); }
+inline KmerSet kmers(const nafgpu_encode_source &src, const KmerOptions &opts = KmerOptions(), int device = -1) { return KmerSet::of(nullptr, &src, opts, device); }
+inline Screens screen(const Selection &sel, const KmerSet &set, const ScreenOptions &opts = ScreenOptions(), int device = -1) {
+    return Screens::of(nullptr, &sel.source(), set, opts, device);
+}
+inline Screens screen(const nafgpu_encode_source &src, const KmerSet &set, const ScreenOptions &opts = ScreenOptions(), int device = -1) {
+    return Screens::of(nullptr, &src, set, opts, device);
+}
 
 // (no counterpart in the reference: the library keeps device memory of closed decoders for the next one -- nafgpu.h)
 inline void trim_device_memory(int device = -1) { (void)nafgpu_trim_device_memory(device); }

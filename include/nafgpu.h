@@ -753,6 +753,96 @@ int nafgpu_trim_decoder(nafgpu_decoder *dec, const nafgpu_trim_opts *opts, nafgp
 int nafgpu_trims_copy_to_host(nafgpu_trims *t, const void *d_ptr, uint64_t n, void *dst);
 void nafgpu_trims_free(nafgpu_trims *t);
 
+/* ---- the k-mers of a reference as a set in HBM, and records screened against it: which records hold k-mers of a known
+ * sequence (a spike-in, a host, a vector: `bbduk ref= k=`, baits), as regions and a keep flag for nafgpu_select ----
+ * Both run in HIP kernels (screen.hip); the letters of the reference and of the reads stay in HBM.  The reference has no
+ * counterpart.  Rules:
+ *   letters   A, C, G, T/U in either case are the codes 0, 1, 2, 3 (the project's 4-bit rule: soft mask and T/U play no part).
+ *             Every other byte is no letter: N, the other IUPAC codes, '-', a byte at or above 128.
+ *   records   record r is positions [d_record_end[r-1], d_record_end[r]) of d_sequence.  d_record_end == NULL or
+ *             n_records == 0: the whole section is record 0 (n_records of the result is 1).  Letters behind the last record
+ *             end belong to no record.  Only d_sequence, n_bases, d_record_end and n_records of the source are read.
+ *   windows   a window is k consecutive positions of ONE record that are all letters; it never spans a record end.
+ *   keys      the forward key of a window is the 2k-bit word with the first letter in the top bits; the reverse complement's
+ *             is that of the letters 3 - c in reverse order.  canonical: the key is min(forward, reverse complement), so
+ *             a read matches either strand of the reference; else the key is the forward one.  The set records the flag and
+ *             a screen uses the set's.
+ *   k         1 .. NAFGPU_KMER_MAX_K = 31: a 64-bit word holds any key and a value for an empty slot besides.  The table
+ *             stores the key itself, so membership is exact: no hash value decides or appears in any output.
+ *   set       nafgpu_kmers_build: n_windows: the windows of the source; n_kmers: their distinct keys; slots: the table's
+ *             words, a power of two at least twice n_windows.  An empty set (n_kmers == 0: every record shorter than k, say)
+ *             is NAFGPU_OK, and nothing matches it.  The set owns its table and outlives its source; it is read only after
+ *             it is built, so any number of screens may use it at once.
+ *   screen    per record r: d_windows[r]: its windows; d_hits[r]: those whose key is in the set; d_regions[r] = {r, a, b, 0}:
+ *             a the start of the first matching window, b the end of the last one, relative to the record, (0, 0) without a
+ *             hit; d_match[r] = hits >= max(min_hits, 1) and hits * 100 >= min_percent * windows; with `interleaved`
+ *             records 2j and 2j+1 are mates and both match when either does; d_keep[r] = match XOR !keep_matched: by
+ *             default what does NOT match is kept (decontamination), keep_matched keeps what matches (baiting).
+ *             d_kept_regions: the whole-record regions {r, 0, L, 0} of the kept records in ascending order, n_kept of them,
+ *             compacted on the device, ready for nafgpu_select once copied to the host.  n_matched, n_windows, n_hits:
+ *             sums over all records; bases_kept: the letters of the kept records.  Integer work only: the result is a
+ *             function of the input alone, whatever the schedule.
+ *   refusals  NAFGPU_E_INVALID_ARG: a NULL argument, opts included; d_sequence == NULL; k of 0 or above 31; for a screen
+ *             also a NULL set, a set built on another device, min_percent > 100, interleaved with an odd number of
+ *             records.  NAFGPU_E_INVALID_LENGTH: a record end below the one in front of it or beyond the section --
+ *             checked on the device, the message names the LOWEST offending record, and no kernel reads outside the
+ *             section or the end table whatever the table holds.  NAFGPU_E_DEVICE: an allocation, copy or kernel failed.
+ *             The _decoder entry points decode first if nothing is decoded yet, make the checks of nafgpu_trim_decoder
+ *             (shard, tiled output, a section that failed, the Length section, NAFGPU_E_IO / NAFGPU_IO_UNEXPECTED_EOF for a
+ *             record end beyond what was decoded), need the sequence decoded and refuse a protein or text archive with
+ *             NAFGPU_E_INVALID_ARG; their error is also kept for nafgpu_last_error.  On any error nothing is produced. */
+#define NAFGPU_KMER_MAX_K 31
+typedef struct {
+    uint8_t k;                   /* 1 .. 31 */
+    uint8_t canonical;           /* used as given; the Python and C++ layers default to 1 */
+    uint8_t reserved[6];
+} nafgpu_kmer_opts;
+typedef struct nafgpu_kmers nafgpu_kmers;              /* owns its table; it outlives its source */
+typedef struct {
+    uint64_t n_windows;                      /* windows in the source */
+    uint64_t n_kmers;                        /* distinct keys */
+    uint64_t n_bases, n_records;
+    uint64_t slots;                          /* words of the table */
+    uint32_t k;
+    uint8_t canonical;
+    uint8_t reserved[3];
+    float ms;                                /* the build kernels, HIP events */
+} nafgpu_kmers_result;
+/* device -1 = current */
+int nafgpu_kmers_build(const nafgpu_encode_source *src, const nafgpu_kmer_opts *opts, int device, nafgpu_kmers **out,
+                       nafgpu_kmers_result *res, nafgpu_error *err);
+int nafgpu_kmers_build_decoder(nafgpu_decoder *dec, const nafgpu_kmer_opts *opts, nafgpu_kmers **out, nafgpu_kmers_result *res,
+                               nafgpu_error *err);
+void nafgpu_kmers_free(nafgpu_kmers *set);
+
+typedef struct {
+    uint8_t keep_matched;        /* 0: keep what does not match; 1: keep what matches */
+    uint8_t interleaved;         /* records 2j and 2j+1 are mates: both match when either does */
+    uint8_t min_percent;         /* 0 .. 100: a record matches only when this share of its windows hits */
+    uint8_t reserved[5];
+    uint64_t min_hits;           /* a record matches only with so many hits; 0 counts as 1 */
+} nafgpu_screen_opts;
+typedef struct nafgpu_screens nafgpu_screens;          /* owns its device buffers, like nafgpu_trims; it outlives source and set */
+typedef struct {
+    const uint64_t *d_windows;               /* n_records */
+    const uint64_t *d_hits;                  /* n_records */
+    const nafgpu_region *d_regions;          /* n_records: {r, a, b, 0} */
+    const uint8_t *d_match;                  /* n_records */
+    const uint8_t *d_keep;                   /* n_records: 1 = kept */
+    const nafgpu_region *d_kept_regions;     /* n_kept: {r, 0, L, 0} of the kept records, ascending */
+    uint64_t n_records, n_matched, n_kept, n_bases;
+    uint64_t n_windows, n_hits, bases_kept;
+    float ms;                                /* the screen kernels, HIP events */
+} nafgpu_screen_result;
+/* device -1 = current */
+int nafgpu_screen(const nafgpu_encode_source *src, const nafgpu_kmers *set, const nafgpu_screen_opts *opts, int device,
+                  nafgpu_screens **out, nafgpu_screen_result *res, nafgpu_error *err);
+int nafgpu_screen_decoder(nafgpu_decoder *dec, const nafgpu_kmers *set, const nafgpu_screen_opts *opts, nafgpu_screens **out,
+                          nafgpu_screen_result *res, nafgpu_error *err);
+/* n bytes from a pointer of the result; NAFGPU_E_INVALID_ARG: a NULL argument, NAFGPU_E_DEVICE: the copy failed */
+int nafgpu_screens_copy_to_host(nafgpu_screens *s, const void *d_ptr, uint64_t n, void *dst);
+void nafgpu_screens_free(nafgpu_screens *s);
+
 /* order-sensitive 64-bit checksum used for full-size parity checks: sum over the 8-byte words w_j of
  * mix64(w_j ^ (j + 1) * K) -- every word is mixed non-linearly with its position before it is added, so
  * byte errors cannot cancel -- see hash64.h */

@@ -9,11 +9,13 @@ from .summary import Summary, summarize  # noqa: F401
 from .search import Hits, search  # noqa: F401
 from .group import Groups, group  # noqa: F401
 from .trim import Trims, trim  # noqa: F401
+from .screen import KmerSet, Screens, kmers, screen  # noqa: F401
 from ._ffi import NafError  # noqa: F401
 
 __version__ = "0.1.0"
 __all__ = ["Decoder", "Encoder", "Record", "open", "NafError", "trim_device_memory", "encode_device", "zstd_compress",
-           "parse_text", "encode_text", "Selection", "Summary", "summarize", "Hits", "search", "Groups", "group", "Trims", "trim"]
+           "parse_text", "encode_text", "Selection", "Summary", "summarize", "Hits", "search", "Groups", "group", "Trims", "trim",
+           "KmerSet", "Screens", "kmers", "screen"]
 
 
 def trim_device_memory(device=-1):

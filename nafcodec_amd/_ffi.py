@@ -171,6 +171,27 @@ class TrimResult(Structure):
                 ("n_bases", c_uint64), ("n_changed", c_uint64), ("bases_in_windows", c_uint64), ("bases_kept", c_uint64), ("ms", c_float)]
 
 
+class KmerOpts(Structure):
+    """nafgpu_kmer_opts: k in 1 .. 31; canonical: a key is the lower of a window's and its reverse complement's."""
+    _fields_ = [("k", c_uint8), ("canonical", c_uint8), ("reserved", c_uint8 * 6)]
+
+
+class KmersResult(Structure):
+    _fields_ = [("n_windows", c_uint64), ("n_kmers", c_uint64), ("n_bases", c_uint64), ("n_records", c_uint64), ("slots", c_uint64),
+                ("k", c_uint32), ("canonical", c_uint8), ("reserved", c_uint8 * 3), ("ms", c_float)]
+
+
+class ScreenOpts(Structure):
+    """nafgpu_screen_opts: which records match a k-mer set and which of them are kept."""
+    _fields_ = [("keep_matched", c_uint8), ("interleaved", c_uint8), ("min_percent", c_uint8), ("reserved", c_uint8 * 5), ("min_hits", c_uint64)]
+
+
+class ScreenResult(Structure):
+    _fields_ = [("d_windows", c_void_p), ("d_hits", c_void_p), ("d_regions", c_void_p), ("d_match", c_void_p), ("d_keep", c_void_p),
+                ("d_kept_regions", c_void_p), ("n_records", c_uint64), ("n_matched", c_uint64), ("n_kept", c_uint64), ("n_bases", c_uint64),
+                ("n_windows", c_uint64), ("n_hits", c_uint64), ("bases_kept", c_uint64), ("ms", c_float)]
+
+
 READ_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, POINTER(c_uint8), c_uint64)
 SEEK_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, c_int64, c_int)
 
@@ -195,6 +216,8 @@ EXPORTS = [
     "nafgpu_search", "nafgpu_search_decoder", "nafgpu_hits_copy_to_host", "nafgpu_hits_free",
     "nafgpu_group", "nafgpu_group_decoder", "nafgpu_groups_copy_to_host", "nafgpu_groups_free",
     "nafgpu_trim", "nafgpu_trim_decoder", "nafgpu_trims_copy_to_host", "nafgpu_trims_free",
+    "nafgpu_kmers_build", "nafgpu_kmers_build_decoder", "nafgpu_kmers_free",
+    "nafgpu_screen", "nafgpu_screen_decoder", "nafgpu_screens_copy_to_host", "nafgpu_screens_free",
 ]
 
 
@@ -319,6 +342,16 @@ class Library:
             L.nafgpu_trims_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
             L.nafgpu_trims_free.argtypes = [c_void_p]
             L.nafgpu_trims_free.restype = None
+        if hasattr(L, "nafgpu_screen"):                      # (absent from older builds loaded for A/B runs)
+            L.nafgpu_kmers_build.argtypes = [POINTER(EncodeSource), POINTER(KmerOpts), c_int, POINTER(c_void_p), POINTER(KmersResult), POINTER(Error)]
+            L.nafgpu_kmers_build_decoder.argtypes = [c_void_p, POINTER(KmerOpts), POINTER(c_void_p), POINTER(KmersResult), POINTER(Error)]
+            L.nafgpu_kmers_free.argtypes = [c_void_p]
+            L.nafgpu_kmers_free.restype = None
+            L.nafgpu_screen.argtypes = [POINTER(EncodeSource), c_void_p, POINTER(ScreenOpts), c_int, POINTER(c_void_p), POINTER(ScreenResult), POINTER(Error)]
+            L.nafgpu_screen_decoder.argtypes = [c_void_p, c_void_p, POINTER(ScreenOpts), POINTER(c_void_p), POINTER(ScreenResult), POINTER(Error)]
+            L.nafgpu_screens_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
+            L.nafgpu_screens_free.argtypes = [c_void_p]
+            L.nafgpu_screens_free.restype = None
 
     # ---- helpers ---------------------------------------------------------------------------
     def zstd_decompress(self, payload: bytes, size: int, device: int = -1) -> bytes:

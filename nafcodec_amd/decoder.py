@@ -324,12 +324,13 @@ class Decoder:
         Python object per region.  A buffer counts as such when its items are bytes or of 32 bytes; an array of integers is
         a list of records like any other.  The Groups of group() stand for their representatives as whole records, in
         order: the first record of every sequence.  The Trims of trim() stand for their kept regions: every kept record cut
-        to its window.  ValueError for what the rules refuse."""
+        to its window; the Screens of screen() for theirs: every kept record, whole.  ValueError for what the rules refuse."""
         from .group import Groups
+        from .screen import Screens
         from .trim import Trims
         if isinstance(regions, Groups):
             regions = regions._regions()
-        elif isinstance(regions, Trims):
+        elif isinstance(regions, (Trims, Screens)):
             regions = regions.kept_regions()
         packed = self._packed_regions(regions)
         if packed is not None:
@@ -415,6 +416,21 @@ class Decoder:
         from .trim import _trim_decoder
         return _trim_decoder(self, cut_front, cut_tail, window, trim_n, min_length, interleaved, quality_base)
 
+    def kmers(self, k=31, canonical=True):
+        """The distinct k-mers of the decoded records as a set in HBM, built on the GPU (decodes first if nothing is decoded
+        yet) -> a KmerSet, which screen() takes and which outlives this decoder.  k: 1 .. 31; canonical: a k-mer and its
+        reverse complement are one key.  See nafcodec_amd.screen."""
+        from .screen import _kmers_decoder
+        return _kmers_decoder(self, k, canonical)
+
+    def screen(self, kmer_set, *, min_hits=1, min_percent=0, interleaved=False, keep_matched=False):
+        """The decoded records against a KmerSet, on the GPU (decodes first if nothing is decoded yet) -> Screens, which
+        select() takes: the kept records, whole.  A record matches with min_hits k-mers of the set in min_percent of its
+        windows; interleaved: mates match together; keep_matched: keep what matches (baiting), not what does not
+        (decontamination).  See nafcodec_amd.screen."""
+        from .screen import _screen_decoder
+        return _screen_decoder(self, kmer_set, min_hits, min_percent, interleaved, keep_matched)
+
 
 class Selection:
     """What Decoder.select() returns: records cut out of a decoded archive, in HBM, with the fields encode_device() reads
@@ -489,6 +505,19 @@ class Selection:
         self._handle()
         return trim(self, cut_front=cut_front, cut_tail=cut_tail, window=window, trim_n=trim_n, min_length=min_length, interleaved=interleaved,
                     quality_base=quality_base, device=device, _lib=self._lib)
+
+    def kmers(self, k=31, canonical=True, *, device=None):
+        """The distinct k-mers of the selected records -> a KmerSet (nafcodec_amd.screen)."""
+        from .screen import kmers
+        self._handle()
+        return kmers(self, k, canonical, device=device, _lib=self._lib)
+
+    def screen(self, kmer_set, *, min_hits=1, min_percent=0, interleaved=False, keep_matched=False, device=None):
+        """The selected records against a KmerSet -> Screens (nafcodec_amd.screen); their records are this selection's."""
+        from .screen import screen
+        self._handle()
+        return screen(self, kmer_set, min_hits=min_hits, min_percent=min_percent, interleaved=interleaved, keep_matched=keep_matched, device=device,
+                      _lib=self._lib)
 
     def close(self):
         if self._h is not None:

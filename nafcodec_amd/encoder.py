@@ -237,6 +237,19 @@ class ParsedText:
         return trim(self, cut_front=cut_front, cut_tail=cut_tail, window=window, trim_n=trim_n, min_length=min_length, interleaved=interleaved,
                     quality_base=quality_base, device=device, _lib=self._lib)
 
+    def kmers(self, k=31, canonical=True, *, device=None):
+        """The distinct k-mers of the parsed records -> a KmerSet (nafcodec_amd.screen)."""
+        from .screen import kmers
+        self._handle()
+        return kmers(self, k, canonical, device=device, _lib=self._lib)
+
+    def screen(self, kmer_set, *, min_hits=1, min_percent=0, interleaved=False, keep_matched=False, device=None):
+        """The parsed records against a KmerSet -> Screens (nafcodec_amd.screen)."""
+        from .screen import screen
+        self._handle()
+        return screen(self, kmer_set, min_hits=min_hits, min_percent=min_percent, interleaved=interleaved, keep_matched=keep_matched, device=device,
+                      _lib=self._lib)
+
     def close(self):
         if self._h is not None:
             h, self._h = self._h, None
