@@ -4,9 +4,10 @@
 // symbol j of a (backward) stream of n symbols then sits at bits [(n - 1 - j) L, (n - j) L) of the stream -- known
 // without decoding symbols 0 .. j - 1.  Nothing of k_huf_decode's serial walk is needed: every 16 bytes of output are
 // produced on their own from the dwords that cover their codes, and stored as one aligned 16-byte piece.
-//   * work unit: one workgroup per stream (<= 128 KiB of symbols), kFlatThreads lanes; lane t owns pieces t, t + 256, ...
+//   * work unit: one workgroup per stream (<= 32 Ki symbols), kFlatThreads lanes; lane t owns pieces t, t + 256, ...
 //     of the destination, so a wave's store instruction writes 1 KB in a row and its loads are dwords in a row
-//     (falling addresses: the stream is read backwards).
+//     (falling addresses: the stream is read backwards).  A lane has 8 (ASCII) or 4 (bytes) pieces in flight: a full
+//     stream of a DNA archive is two rounds of the workgroup.
 //   * table: the workgroup stages its tree once from the pool (2^L entries of len << 8 | sym) as a table indexed by
 //     one code (L > 4) or two codes (L <= 4) whose entries hold the bytes to emit (ASCII: byte_chars of each symbol).
 //   * edges: the first and the last piece of a stream may hold bytes of a neighbour, or none: they go out byte-wise.
@@ -34,8 +35,22 @@ namespace {
 #define NAFGPU_FLAT_INLINE __forceinline__
 #endif
 
-constexpr uint32_t kFlatThreads = 256;
-constexpr uint32_t kFlatUnroll = 4;                    // pieces per lane in flight (flat_stream)
+// The geometry: lanes per stream, and pieces a lane has in flight per round -- by output mode, because a piece in flight
+// costs the byte-mode kernel more registers (72 VGPRs at 4, 137 at 8) than the ASCII one (58 at 4, 100 at 8).  Measured on
+// the headline archive (profiles/r06_flat_geometry_probe.log): 256 x 8 is 9 % faster than 256 x 4 at
+// half its waves per SIMD; 64 and 128 lanes, 512 lanes, and 2, 6, 12 or 16 pieces are no faster than 256 x 4.  The level-3
+// leg, where the byte mode runs, does not tell 4 from 8.  Experiment builds override the three values (tools/flat_geometry.sh).
+#ifndef NAFGPU_FLAT_THREADS
+#define NAFGPU_FLAT_THREADS 256
+#endif
+#ifndef NAFGPU_FLAT_UNROLL_ASCII
+#define NAFGPU_FLAT_UNROLL_ASCII 8
+#endif
+#ifndef NAFGPU_FLAT_UNROLL_BYTES
+#define NAFGPU_FLAT_UNROLL_BYTES 4
+#endif
+constexpr uint32_t kFlatThreads = NAFGPU_FLAT_THREADS;
+constexpr uint32_t kFlatUnrollAscii = NAFGPU_FLAT_UNROLL_ASCII, kFlatUnrollBytes = NAFGPU_FLAT_UNROLL_BYTES;
 
 __device__ inline void flat_flag_error(uint32_t *status, uint32_t code, uint32_t detail) {
     if (atomicCAS(&status[0], 0u, code) == 0u) status[1] = detail;
@@ -58,6 +73,7 @@ __device__ NAFGPU_FLAT_INLINE void flat_stream(const uint8_t *sp, uint32_t n, ui
                                    uint32_t *s_tbl) {
     constexpr uint32_t kOutB = ASCII ? 2 : 1;              // output bytes per symbol
     constexpr uint32_t kSyms = 16 / kOutB;                 // symbols per piece
+    constexpr uint32_t kFlatUnroll = ASCII ? kFlatUnrollAscii : kFlatUnrollBytes;   // pieces per lane in flight
     constexpr uint32_t kPer = L <= 4 ? 2 : 1;              // symbols per look-up
     constexpr uint32_t kIdxBits = kPer * L;
     constexpr uint32_t kLookB = kPer * kOutB;              // bytes per look-up: 1, 2 or 4
@@ -80,8 +96,9 @@ __device__ NAFGPU_FLAT_INLINE void flat_stream(const uint8_t *sp, uint32_t n, ui
     // Pieces [pf0, pf1) lie inside the stream; piece 0 (h > 0) and piece pf1 (the stream ends inside it) are its edges.
     const uint32_t end = h + n * kOutB;
     const uint32_t pf0 = h ? 1u : 0u, pf1 = end >> 4;
-    // Whole pieces, kFlatUnroll per lane and round (pieces p, p + 256, ...), the dwords of the next round requested
-    // before the pieces of this one are stored: memory operations retire in order, so a wait for loads issued BEHIND
+    // Whole pieces, kFlatUnroll per lane and round (pieces p, p + 256, ...: a round of the workgroup covers
+    // kFlatThreads * kFlatUnroll pieces in a row), the dwords of the next round requested before the pieces of this one
+    // are stored: memory operations retire in order, so a wait for loads issued BEHIND
     // stores waits for the stores too -- a round trip per kilobyte and wave, 4.3 TB/s (profiles/).  Requested in front of
     // them the loads are waited for with the stores still in flight.
     // Piece p holds symbols j0 .. j0 + kSyms - 1, j0 = (16 p - h) / kOutB (ASCII: h is even, a symbol never straddles
@@ -160,7 +177,7 @@ __device__ NAFGPU_FLAT_INLINE void flat_stream(const uint8_t *sp, uint32_t n, ui
 
 // grid: 64 workgroups per task, workgroup k of a task takes its k-th stream
 template <bool ASCII>
-__global__ __launch_bounds__(256) void k_huf_flat(const uint8_t *__restrict__ src, const HufTask *__restrict__ tasks,
+__global__ __launch_bounds__(kFlatThreads) void k_huf_flat(const uint8_t *__restrict__ src, const HufTask *__restrict__ tasks,
                                                   const HufTblCopy *__restrict__ copies, const HufStream *__restrict__ streams,
                                                   const uint16_t *__restrict__ pool, const uint64_t *__restrict__ blk_base,
                                                   uint8_t *dst_base, uint32_t t_char, uint32_t *status) {
