@@ -352,6 +352,80 @@ private:
     nafgpu_trim_result res_{};
 };
 
+// (no counterpart in the reference) where read 1 and the reverse complement of read 2 of every pair of mates (records 2j and
+// 2j + 1) overlap, found on the GPU: nafgpu_overlap has the rules.
+struct OverlapOptions {
+    unsigned min_overlap = 30;       // an accepted shift has so many matching letters
+    unsigned max_mismatches = 5;     // at most so many mismatches
+    unsigned max_mismatch_percent = 20;   // and at most this share of them among matches + mismatches
+    unsigned quality_base = 33;      // what Decoder::merge writes the quality of disagreeing letters from
+};
+// What overlap returns: an Overlaps owns its device buffers and outlives its source; the accessors copy a table to the host.
+// Move-only.
+class Overlaps {
+public:
+    Overlaps(Overlaps &&o) noexcept : o_(std::exchange(o.o_, nullptr)), res_(o.res_) {}
+    Overlaps &operator=(Overlaps &&o) noexcept {
+        if (this != &o) {
+            nafgpu_overlaps_free(o_);
+            o_ = std::exchange(o.o_, nullptr);
+            res_ = o.res_;
+        }
+        return *this;
+    }
+    Overlaps(const Overlaps &) = delete;
+    ~Overlaps() { nafgpu_overlaps_free(o_); }
+
+    const nafgpu_overlap_result &result() const { return res_; }
+    const nafgpu_overlaps *raw() const { return o_; }
+    uint64_t n_records() const { return res_.n_records; }
+    uint64_t n_pairs() const { return res_.n_pairs; }
+    uint64_t n_found() const { return res_.n_found; }
+    uint64_t n_too_long() const { return res_.n_too_long; }
+    uint64_t n_unmerged() const { return res_.n_unmerged; }
+    uint64_t n_cut() const { return res_.n_cut; }
+    uint64_t matches() const { return res_.matches; }
+    uint64_t mismatches() const { return res_.mismatches; }
+    uint64_t bases_merged() const { return res_.bases_merged; }
+    uint64_t bases_after_cut() const { return res_.bases_after_cut; }
+    float ms() const { return res_.ms; }
+    std::vector<nafgpu_pair_overlap> pairs() const { return table(res_.d_pairs, res_.n_pairs); }
+    std::vector<nafgpu_region> regions() const { return table(res_.d_regions, res_.n_records); }               // the adapter cut, ready for nafgpu_select
+    std::vector<nafgpu_region> unmerged_regions() const { return table(res_.d_unmerged_regions, res_.n_unmerged); }
+
+    // dec null: the pairs of `src`; else the decoder's (it decodes first if nothing is decoded yet)
+    static Overlaps of(nafgpu_decoder *dec, const nafgpu_encode_source *src, const OverlapOptions &opts, int device) {
+        nafgpu_overlap_opts o{};
+        o.min_overlap = opts.min_overlap;
+        o.max_mismatches = opts.max_mismatches;
+        o.max_mismatch_percent = static_cast<uint8_t>(opts.max_mismatch_percent > 255 ? 255 : opts.max_mismatch_percent);
+        o.quality_base = static_cast<uint8_t>(opts.quality_base > 255 ? 255 : opts.quality_base);
+        nafgpu_overlaps *h = nullptr;
+        nafgpu_overlap_result r;
+        nafgpu_error e{};
+        const int rc = dec ? nafgpu_overlap_decoder(dec, &o, &h, &r, &e) : nafgpu_overlap(src, &o, device, &h, &r, &e);
+        if (rc != NAFGPU_OK) throw Error(e);
+        return Overlaps(h, r);
+    }
+
+private:
+    Overlaps(nafgpu_overlaps *o, const nafgpu_overlap_result &r) : o_(o), res_(r) {}
+    template <class T>
+    std::vector<T> table(const T *d_ptr, uint64_t n) const {
+        std::vector<T> out(d_ptr ? static_cast<size_t>(n) : 0);
+        const int rc = out.empty() ? NAFGPU_OK : nafgpu_overlaps_copy_to_host(o_, d_ptr, sizeof(T) * n, out.data());
+        if (rc != NAFGPU_OK) {
+            nafgpu_error e{};
+            e.status = rc;
+            std::snprintf(e.message, sizeof e.message, "nafgpu_overlaps_copy_to_host: %s", rc == NAFGPU_E_DEVICE ? "the copy failed" : "a null argument");
+            throw Error(e);
+        }
+        return out;
+    }
+    nafgpu_overlaps *o_ = nullptr;
+    nafgpu_overlap_result res_{};
+};
+
 // (no counterpart in the reference) the k-mers of a reference as a set in HBM, and records screened against it:
 // nafgpu_kmers_build and nafgpu_screen have the rules.
 struct KmerOptions {
@@ -616,6 +690,27 @@ public:
         nafgpu_select_result r;
         nafgpu_error e{};
         if (nafgpu_select(d_, regions.data(), regions.size(), &o, &s, &r, &e) != NAFGPU_OK) throw Error(e);
+        return Selection(s, r);
+    }
+    // (no counterpart in the reference) where the mates of every decoded pair overlap (decodes first if nothing is decoded yet)
+    Overlaps overlap(const OverlapOptions &opts = OverlapOptions()) { return Overlaps::of(d_, nullptr, opts, -1); }
+    // every record, cut where it reads into the adapter
+    Selection select(const Overlaps &overlaps, bool name_regions = false) {
+        const std::vector<nafgpu_region> regions = overlaps.regions();
+        nafgpu_select_opts o{};
+        o.name_regions = name_regions ? 1 : 0;
+        nafgpu_selection *s = nullptr;
+        nafgpu_select_result r;
+        nafgpu_error e{};
+        if (nafgpu_select(d_, regions.data(), regions.size(), &o, &s, &r, &e) != NAFGPU_OK) throw Error(e);
+        return Selection(s, r);
+    }
+    // the found pairs of this decoder's overlaps joined into one record each, in pair order
+    Selection merge(const Overlaps &overlaps) {
+        nafgpu_selection *s = nullptr;
+        nafgpu_select_result r;
+        nafgpu_error e{};
+        if (nafgpu_merge_pairs(d_, overlaps.raw(), &s, &r, &e) != NAFGPU_OK) throw Error(e);
         return Selection(s, r);
     }
     // (no counterpart in the reference) where `patterns` occur in the decoded records (decodes first if nothing is decoded yet)
@@ -913,6 +1008,10 @@ inline Screens screen(const Selection &sel, const KmerSet &set, const ScreenOpti
 inline Screens screen(const nafgpu_encode_source &src, const KmerSet &set, const ScreenOptions &opts = ScreenOptions(), int device = -1) {
     return Screens::of(nullptr, &src, set, opts, device);
 }
+
+// the overlaps of a selection index the selection's records
+inline Overlaps overlap(const Selection &sel, const OverlapOptions &opts = OverlapOptions(), int device = -1) { return Overlaps::of(nullptr, &sel.source(), opts, device); }
+inline Overlaps overlap(const nafgpu_encode_source &src, const OverlapOptions &opts = OverlapOptions(), int device = -1) { return Overlaps::of(nullptr, &src, opts, device); }
 
 // (no counterpart in the reference: the library keeps device memory of closed decoders for the next one -- nafgpu.h)
 inline void trim_device_memory(int device = -1) { (void)nafgpu_trim_device_memory(device); }

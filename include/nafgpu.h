@@ -843,6 +843,92 @@ int nafgpu_screen_decoder(nafgpu_decoder *dec, const nafgpu_kmers *set, const na
 int nafgpu_screens_copy_to_host(nafgpu_screens *s, const void *d_ptr, uint64_t n, void *dst);
 void nafgpu_screens_free(nafgpu_screens *s);
 
+/* ---- paired reads in HBM -> where read 1 and the reverse complement of read 2 overlap: the cut that takes read-through
+ * adapters off both mates (`fastp`'s default for pairs), as regions for nafgpu_select, and the pair joined into one fragment
+ * (`fastp -m`, FLASH, `bbmerge`, `vsearch --fastq_mergepairs`) as a selection ----
+ * Every shift of every pair is compared in HIP kernels (overlap.hip); the letters stay in HBM, the answer is 32 bytes per pair
+ * and 32 per record.  The reference has no counterpart.  Rules:
+ *   letters   A, C, G, T/U in either case are the codes 0, 1, 2, 3, as in nafgpu_screen.  Every other byte is no letter.
+ *   pairs     records 2j (R1: letters x, length n1) and 2j+1 (R2: length n2) are pair j.  y is R2 reversed and complemented:
+ *             y[i] = 3 - code(R2[n2-1-i]); a non-letter stays a non-letter.  Letters behind the last record end belong to no
+ *             record.
+ *   shifts    a shift d in -(n2-1) .. n1-1 puts y[i] under x[i+d].  The positions compared are p in [max(0,d), min(n1,d+n2));
+ *             `compared` is their number.  At such a position both letters and equal is a match, both letters and different
+ *             a mismatch, anything else neutral.  insert = d + n2 is the fragment's length; d < 0 is a fragment shorter than
+ *             R2, where both mates read into the adapter.
+ *   accepted  matches >= max(min_overlap, 1), mismatches <= max_mismatches and
+ *             mismatches * 100 <= max_mismatch_percent * (matches + mismatches).
+ *   best      among the accepted shifts the fewest mismatches, then the most matches, then the lowest d.  No accepted shift:
+ *             the pair is not found.
+ *   cap       a pair with a mate longer than NAFGPU_OVERLAP_MAX_LENGTH letters is flagged too_long: it is not analysed and
+ *             not found, and it is no refusal.  A pair with an empty mate is not found.
+ *   output    d_pairs[j]: shift, insert, matches, mismatches, compared, found, too_long; everything but too_long is 0 when
+ *             the pair is not found.  d_regions[r] = {r, 0, min(L, insert), 0} when r's pair is found, else {r, 0, L, 0}:
+ *             the adapter cut, ready for nafgpu_select once copied to the host.  d_unmerged_regions: the whole-record regions
+ *             {r, 0, L, 0} of both mates of every pair not found, ascending, n_unmerged of them, compacted on the device.
+ *             n_cut: records whose region is shorter than L; matches, mismatches, bases_merged (the inserts): sums over the
+ *             found pairs; bases_after_cut: the letters of all regions.  Integer work only: the result is a function of the
+ *             input alone, whatever the schedule.
+ *   merge     nafgpu_merge_pairs: a selection with one record per FOUND pair, in pair order, of `insert` positions p.
+ *             p < d (only R1 covers it): R1's byte and quality byte as they lie.  p >= n1 (only R2 covers it): the byte
+ *             R2[n2-1-(p-d)] through nafgpu_select's complement table, case kept, and its quality byte.  Else both cover p,
+ *             with bytes a (R1), b (R2, complemented) and quality bytes qa, qb: the letter is b if qb > qa, else a (without
+ *             qualities always a); the quality byte is max(qa, qb) when a and b are letters with equal codes, otherwise
+ *             quality_base + max(|qa - qb|, 2), at most 255.  Id and comment are R1's.  The selection is an ordinary one:
+ *             nafgpu_encode_device, nafgpu_selection_format and the record jobs take it.
+ *   refusals  NAFGPU_E_INVALID_ARG: a NULL argument, opts included; d_sequence == NULL; no record table (d_record_end == NULL
+ *             or n_records == 0); an odd number of records; max_mismatch_percent > 100.  NAFGPU_E_INVALID_LENGTH: a record
+ *             end below the one in front of it or beyond the section -- checked on the device, the message names the LOWEST
+ *             offending record, and no kernel reads outside the section or the end table whatever the table holds.
+ *             NAFGPU_E_DEVICE: an allocation, copy or kernel failed.
+ *             nafgpu_overlap_decoder makes the checks of nafgpu_trim_decoder (it decodes first if nothing is decoded yet;
+ *             shard, tiled output, a section that failed, the Length section, NAFGPU_E_IO / NAFGPU_IO_UNEXPECTED_EOF for a
+ *             record end beyond what was decoded), needs the sequence decoded and refuses a protein or text archive with
+ *             NAFGPU_E_INVALID_ARG; its error is also kept for nafgpu_last_error.
+ *             nafgpu_merge_pairs refuses what nafgpu_select refuses, and with NAFGPU_E_INVALID_ARG: a NULL argument;
+ *             overlaps whose n_records differs from the decoder's, that were found on another device, or whose pairs do not
+ *             fit the decoder's records (the message names the LOWEST such pair); a protein or text archive; a decoder
+ *             without the sequence decoded.  On any error nothing is produced. */
+#define NAFGPU_OVERLAP_MAX_LENGTH 1024
+typedef struct {
+    uint32_t min_overlap;        /* an accepted shift has so many matches; 0 counts as 1 */
+    uint32_t max_mismatches;     /* and at most so many mismatches */
+    uint8_t max_mismatch_percent;   /* 0 .. 100: and at most this share of mismatches among matches + mismatches */
+    uint8_t quality_base;        /* what a quality byte of value 0 is written as: 33 for today's FASTQ (used as given, by the merge) */
+    uint8_t reserved[6];
+} nafgpu_overlap_opts;
+typedef struct {
+    int64_t shift;               /* d */
+    uint64_t insert;             /* d + n2 */
+    uint32_t matches, mismatches, compared;
+    uint8_t found, too_long;
+    uint8_t reserved[2];
+} nafgpu_pair_overlap;
+typedef struct nafgpu_overlaps nafgpu_overlaps;        /* owns its device buffers, like nafgpu_trims; it outlives its source */
+typedef struct {
+    const nafgpu_pair_overlap *d_pairs;      /* n_pairs */
+    const nafgpu_region *d_regions;          /* n_records: {r, 0, min(L, insert), 0}: the adapter cut */
+    const nafgpu_region *d_unmerged_regions; /* n_unmerged: {r, 0, L, 0} of both mates of every pair not found, ascending */
+    uint64_t n_records, n_pairs, n_bases;
+    uint64_t n_found, n_too_long, n_unmerged;
+    uint64_t n_cut;                          /* records whose region is shorter than L */
+    uint64_t matches, mismatches;            /* sums over the found pairs */
+    uint64_t bases_merged;                   /* the sum of insert over the found pairs */
+    uint64_t bases_after_cut;                /* the letters of all regions */
+    float ms;                                /* the overlap kernels, HIP events */
+} nafgpu_overlap_result;
+/* device -1 = current */
+int nafgpu_overlap(const nafgpu_encode_source *src, const nafgpu_overlap_opts *opts, int device, nafgpu_overlaps **out,
+                   nafgpu_overlap_result *res, nafgpu_error *err);
+int nafgpu_overlap_decoder(nafgpu_decoder *dec, const nafgpu_overlap_opts *opts, nafgpu_overlaps **out,
+                           nafgpu_overlap_result *res, nafgpu_error *err);
+/* one record per found pair; the selection is freed with nafgpu_selection_free and outlives decoder and overlaps */
+int nafgpu_merge_pairs(nafgpu_decoder *dec, const nafgpu_overlaps *overlaps, nafgpu_selection **out, nafgpu_select_result *res,
+                       nafgpu_error *err);
+/* n bytes from a pointer of the result; NAFGPU_E_INVALID_ARG: a NULL argument, NAFGPU_E_DEVICE: the copy failed */
+int nafgpu_overlaps_copy_to_host(nafgpu_overlaps *o, const void *d_ptr, uint64_t n, void *dst);
+void nafgpu_overlaps_free(nafgpu_overlaps *o);
+
 /* order-sensitive 64-bit checksum used for full-size parity checks: sum over the 8-byte words w_j of
  * mix64(w_j ^ (j + 1) * K) -- every word is mixed non-linearly with its position before it is added, so
  * byte errors cannot cancel -- see hash64.h */

@@ -10,12 +10,13 @@ from .search import Hits, search  # noqa: F401
 from .group import Groups, group  # noqa: F401
 from .trim import Trims, trim  # noqa: F401
 from .screen import KmerSet, Screens, kmers, screen  # noqa: F401
+from .overlap import Overlaps, overlap  # noqa: F401
 from ._ffi import NafError  # noqa: F401
 
 __version__ = "0.1.0"
 __all__ = ["Decoder", "Encoder", "Record", "open", "NafError", "trim_device_memory", "encode_device", "zstd_compress",
            "parse_text", "encode_text", "Selection", "Summary", "summarize", "Hits", "search", "Groups", "group", "Trims", "trim",
-           "KmerSet", "Screens", "kmers", "screen"]
+           "KmerSet", "Screens", "kmers", "screen", "Overlaps", "overlap"]
 
 
 def trim_device_memory(device=-1):

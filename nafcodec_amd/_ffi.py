@@ -192,6 +192,24 @@ class ScreenResult(Structure):
                 ("n_windows", c_uint64), ("n_hits", c_uint64), ("bases_kept", c_uint64), ("ms", c_float)]
 
 
+class OverlapOpts(Structure):
+    """nafgpu_overlap_opts: which shifts of a pair of mates are accepted; quality_base is used by the merge."""
+    _fields_ = [("min_overlap", c_uint32), ("max_mismatches", c_uint32), ("max_mismatch_percent", c_uint8), ("quality_base", c_uint8),
+                ("reserved", c_uint8 * 6)]
+
+
+class PairOverlap(Structure):
+    """nafgpu_pair_overlap: the best accepted shift of a pair; all 0 (but too_long) when the pair is not found."""
+    _fields_ = [("shift", c_int64), ("insert", c_uint64), ("matches", c_uint32), ("mismatches", c_uint32), ("compared", c_uint32),
+                ("found", c_uint8), ("too_long", c_uint8), ("reserved", c_uint8 * 2)]
+
+
+class OverlapResult(Structure):
+    _fields_ = [("d_pairs", c_void_p), ("d_regions", c_void_p), ("d_unmerged_regions", c_void_p), ("n_records", c_uint64), ("n_pairs", c_uint64),
+                ("n_bases", c_uint64), ("n_found", c_uint64), ("n_too_long", c_uint64), ("n_unmerged", c_uint64), ("n_cut", c_uint64),
+                ("matches", c_uint64), ("mismatches", c_uint64), ("bases_merged", c_uint64), ("bases_after_cut", c_uint64), ("ms", c_float)]
+
+
 READ_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, POINTER(c_uint8), c_uint64)
 SEEK_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, c_int64, c_int)
 
@@ -218,6 +236,7 @@ EXPORTS = [
     "nafgpu_trim", "nafgpu_trim_decoder", "nafgpu_trims_copy_to_host", "nafgpu_trims_free",
     "nafgpu_kmers_build", "nafgpu_kmers_build_decoder", "nafgpu_kmers_free",
     "nafgpu_screen", "nafgpu_screen_decoder", "nafgpu_screens_copy_to_host", "nafgpu_screens_free",
+    "nafgpu_overlap", "nafgpu_overlap_decoder", "nafgpu_merge_pairs", "nafgpu_overlaps_copy_to_host", "nafgpu_overlaps_free",
 ]
 
 
@@ -352,6 +371,13 @@ class Library:
             L.nafgpu_screens_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
             L.nafgpu_screens_free.argtypes = [c_void_p]
             L.nafgpu_screens_free.restype = None
+        if hasattr(L, "nafgpu_overlap"):                     # (absent from older builds loaded for A/B runs)
+            L.nafgpu_overlap.argtypes = [POINTER(EncodeSource), POINTER(OverlapOpts), c_int, POINTER(c_void_p), POINTER(OverlapResult), POINTER(Error)]
+            L.nafgpu_overlap_decoder.argtypes = [c_void_p, POINTER(OverlapOpts), POINTER(c_void_p), POINTER(OverlapResult), POINTER(Error)]
+            L.nafgpu_merge_pairs.argtypes = [c_void_p, c_void_p, POINTER(c_void_p), POINTER(SelectResult), POINTER(Error)]
+            L.nafgpu_overlaps_copy_to_host.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
+            L.nafgpu_overlaps_free.argtypes = [c_void_p]
+            L.nafgpu_overlaps_free.restype = None
 
     # ---- helpers ---------------------------------------------------------------------------
     def zstd_decompress(self, payload: bytes, size: int, device: int = -1) -> bytes:

@@ -1,5 +1,5 @@
 // select.cpp -- host side of nafgpu_select / nafgpu_find_records and the owner of a selection's buffers.  The kernels are
-// in select.hip; the rules in include/nafgpu.h.
+// in select.hip; the rules in include/nafgpu.h.  nafgpu_merge_pairs is here too: it makes a selection (its kernels: overlap.hip).
 //
 // Two round trips: the host reads the status words and the three totals of the size pass, allocates the outputs by them,
 // and waits for the gather.  Beside the outputs: 32 bytes per region (the regions themselves), 8 for where its letters lie,
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "device.h"
+#include "overlap.h"
 
 using namespace nafgpu;
 using namespace nafgpu::sel;
@@ -192,6 +193,97 @@ Failure select(const SelSource &s, const nafgpu_region *regions, uint64_t n, boo
     return Failure();
 }
 
+// nafgpu_merge_pairs: one record per found pair.  The passes of select() with the kernels of overlap.hip in the place of the
+// size pass and the gather; ids and comments are R1's, copied by k_sel_strings.
+Failure merge_pairs(const SelSource &s, const ovl::OvlView &v, std::unique_ptr<nafgpu_selection> &out) {
+    auto refuse = [](const std::string &what) { return Failure::make(NAFGPU_E_INVALID_ARG, "merge_pairs: " + what); };
+    if (s.sequence_type > 1) return refuse("mates need a nucleotide archive (dna or rna)");
+    if (!s.seq) return refuse("the sequence field is needed");
+    if (v.n_records != s.n_rec) return refuse("the overlaps are of " + std::to_string(v.n_records) + " records, the decoder has " + std::to_string(s.n_rec));
+    if (v.device != s.device) return refuse("the overlaps were found on another device");
+    std::unique_ptr<nafgpu_selection> sel;
+    if (!open_selection(s, sel)) return device_failure("no stream");
+    hipStream_t stream = sel->stream;
+    Events ev;
+    if (!ev.create()) return device_failure("hipEventCreate failed");
+    const bool with_ids = s.ids != nullptr, with_com = s.com != nullptr;
+    const uint64_t n = v.n_found, n_pairs = v.n_pairs;
+
+    ScanTotals tot[4];
+    std::memset(tot, 0, sizeof tot);
+    uint32_t status[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint8_t table[256];
+    complement_table(s.sequence_type, table);
+    DevBuf d_regions, d_pair_of, d_where, d_table;
+    if (!d_regions.alloc_items(std::max<uint64_t>(n, 1), sizeof(nafgpu_region)) || !d_pair_of.alloc_items(std::max<uint64_t>(n, 1), 8) ||
+        !d_where.alloc_items(n_pairs + 1, 8) || !alloc_ends(sel->d_len, n) || (with_ids && !alloc_ends(sel->d_id_off, n)) ||
+        (with_com && !alloc_ends(sel->d_com_off, n)) || !sel->d_scan_tmp.alloc(scan_tmp_bytes(std::max(n, n_pairs) + 1)) || !sel->d_totals.alloc(sizeof tot) ||
+        !sel->d_status.alloc(sizeof status) || !d_table.alloc(sizeof table))
+        return device_failure("out of device memory");
+    uint64_t *len = excl_of(sel->d_len), *id_size = with_ids ? excl_of(sel->d_id_off) : nullptr, *com_size = with_com ? excl_of(sel->d_com_off) : nullptr;
+    ScanTotals *d_tot = sel->d_totals.as<ScanTotals>();
+    uint32_t *d_status = sel->d_status.as<uint32_t>();
+    ovl::OvlSource os;
+    os.seq = s.seq;  os.qual = s.qual;  os.n_seq = s.n_seq;  os.n_qual = s.n_qual;
+    os.rec_end = s.rec_end;  os.n_rec = s.n_rec;
+    os.ids = s.ids;  os.id_end = s.id_end;  os.n_ids = s.n_ids;
+    os.com = s.com;  os.com_end = s.com_end;  os.n_com = s.n_com;
+    bool ok = hipMemcpyAsync(d_tot, tot, sizeof tot, hipMemcpyHostToDevice, stream) == hipSuccess &&
+              hipMemcpyAsync(d_status, status, sizeof status, hipMemcpyHostToDevice, stream) == hipSuccess &&
+              hipMemcpyAsync(d_table.bytes(), table, sizeof table, hipMemcpyHostToDevice, stream) == hipSuccess &&
+              hipEventRecord(ev.ev[0], stream) == hipSuccess;
+    if (!ok) return drained_failure(stream, "host-to-device copy failed");
+    ovl::launch_ovl_found(stream, v.pairs, n_pairs, d_where.as<uint64_t>());
+    launch_scan_excl_u64(stream, d_where.as<uint64_t>(), n_pairs + 1, d_where.as<uint64_t>(), sel->d_scan_tmp.bytes(), &d_tot[3], d_status);
+    ovl::launch_ovl_merge_sizes(stream, v.pairs, n_pairs, d_where.as<uint64_t>(), n, os, len, id_size, com_size, d_pair_of.as<uint64_t>(),
+                                d_regions.as<nafgpu_region>(), d_status);
+    launch_scan_excl_u64(stream, len, n + 1, len, sel->d_scan_tmp.bytes(), &d_tot[0], d_status);
+    if (with_ids) launch_scan_excl_u64(stream, id_size, n + 1, id_size, sel->d_scan_tmp.bytes(), &d_tot[1], d_status);
+    if (with_com) launch_scan_excl_u64(stream, com_size, n + 1, com_size, sel->d_scan_tmp.bytes(), &d_tot[2], d_status);
+    ok = hipGetLastError() == hipSuccess && hipEventRecord(ev.ev[1], stream) == hipSuccess &&
+         hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, stream) == hipSuccess &&
+         hipMemcpyAsync(status, d_status, sizeof status, hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+    if (!ok) return drained_failure(stream, "the size pass failed");
+    if (tot[3].sum != n) return refuse("the overlaps hold " + std::to_string(tot[3].sum) + " found pairs, their totals say " + std::to_string(n));
+    if (status[0] & ovl::kOvlStRefused) return refuse("pair " + std::to_string(complement_at(status, 2)) + " does not fit the decoder's records");
+    if (status[0] & ovl::kOvlStBeyond)
+        return Failure::io(NAFGPU_IO_UNEXPECTED_EOF, "pair " + std::to_string(complement_at(status, 4)) + ": record lengths exceed the decoded sequence");
+    const uint64_t n_out = tot[0].sum, n_ids_bytes = with_ids ? tot[1].sum : 0, n_com_bytes = with_com ? tot[2].sum : 0;
+
+    const uint64_t n_alloc = std::max<uint64_t>((n_out + 15) / 16 * 16, 16);
+    if (!sel->d_seq.alloc(n_alloc) || (s.qual && !sel->d_qual.alloc(n_alloc)) || (with_ids && !sel->d_ids.alloc(std::max<uint64_t>(n_ids_bytes, 16))) ||
+        (with_com && !sel->d_com.alloc(std::max<uint64_t>(n_com_bytes, 16))))
+        return device_failure("out of device memory");
+    ok = hipEventRecord(ev.ev[2], stream) == hipSuccess;
+    ovl::launch_ovl_merge(stream, v.pairs, d_pair_of.as<uint64_t>(), len, n, n_out, os, d_table.bytes(), v.quality_base, sel->d_seq.bytes(),
+                          s.qual ? sel->d_qual.bytes() : nullptr);
+    launch_sel_strings(stream, d_regions.as<nafgpu_region>(), n, s, false, len, id_size, with_ids ? sel->d_ids.bytes() : nullptr, com_size,
+                       with_com ? sel->d_com.bytes() : nullptr);
+    ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(ev.ev[3], stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
+    if (!ok) return drained_failure(stream, "the merge failed");
+    float a = 0, b = 0, ms = 0;
+    if (hipEventElapsedTime(&a, ev.ev[0], ev.ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev.ev[2], ev.ev[3]) == hipSuccess) ms = a + b;
+
+    nafgpu_select_result &r = sel->res;
+    std::memset(&r, 0, sizeof r);
+    r.src.d_sequence = sel->d_seq.bytes();
+    r.src.n_bases = n_out;
+    r.src.d_quality = s.qual ? sel->d_qual.bytes() : nullptr;
+    r.src.n_quality = s.qual ? n_out : 0;
+    r.src.d_record_end = len + 1;
+    r.src.n_records = n;
+    r.src.d_ids = with_ids ? sel->d_ids.bytes() : nullptr;
+    r.src.n_ids_bytes = n_ids_bytes;
+    r.src.d_comments = with_com ? sel->d_com.bytes() : nullptr;
+    r.src.n_comments_bytes = n_com_bytes;
+    r.d_id_end = with_ids ? id_size + 1 : nullptr;
+    r.d_comment_end = with_com ? com_size + 1 : nullptr;
+    r.n_regions = n;
+    r.ms = ms;
+    out = std::move(sel);
+    return Failure();
+}
+
 Failure find_records(const SelSource &s, const uint8_t *names, uint64_t n_bytes, uint64_t n_names, uint64_t *record_out) {
     if (!s.ids) return Failure::make(NAFGPU_E_INVALID_ARG, "find_records needs the ids decoded (opts.id)");
     std::vector<uint64_t> name_end;
@@ -295,6 +387,22 @@ int nafgpu_select(nafgpu_decoder *dec, const nafgpu_region *regions, uint64_t n_
     if (!f.ok()) return decoder_fail(dec, f, err);
     std::unique_ptr<nafgpu_selection> sel;
     f = select(s, regions, n_regions, opts && opts->name_regions, sel);
+    if (!f.ok()) return decoder_fail(dec, f, err);
+    *res = sel->res;
+    *out = sel.release();
+    return fail_c(err, Failure());
+}
+
+int nafgpu_merge_pairs(nafgpu_decoder *dec, const nafgpu_overlaps *overlaps, nafgpu_selection **out, nafgpu_select_result *res, nafgpu_error *err) {
+    if (out) *out = nullptr;
+    if (res) std::memset(res, 0, sizeof *res);
+    if (!dec) return fail_c(err, Failure::make(NAFGPU_E_INVALID_ARG, "null argument"));
+    if (!overlaps || !out || !res) return decoder_fail(dec, Failure::make(NAFGPU_E_INVALID_ARG, "null argument"), err);
+    SelSource s;
+    Failure f = decoder_source(dec, true, &s);
+    if (!f.ok()) return decoder_fail(dec, f, err);
+    std::unique_ptr<nafgpu_selection> sel;
+    f = merge_pairs(s, ovl::view_of(overlaps), sel);
     if (!f.ok()) return decoder_fail(dec, f, err);
     *res = sel->res;
     *out = sel.release();

@@ -324,14 +324,18 @@ class Decoder:
         Python object per region.  A buffer counts as such when its items are bytes or of 32 bytes; an array of integers is
         a list of records like any other.  The Groups of group() stand for their representatives as whole records, in
         order: the first record of every sequence.  The Trims of trim() stand for their kept regions: every kept record cut
-        to its window; the Screens of screen() for theirs: every kept record, whole.  ValueError for what the rules refuse."""
+        to its window; the Screens of screen() for theirs: every kept record, whole; the Overlaps of overlap() for their regions:
+        every record, cut where it reads into the adapter.  ValueError for what the rules refuse."""
         from .group import Groups
+        from .overlap import Overlaps
         from .screen import Screens
         from .trim import Trims
         if isinstance(regions, Groups):
             regions = regions._regions()
         elif isinstance(regions, (Trims, Screens)):
             regions = regions.kept_regions()
+        elif isinstance(regions, Overlaps):
+            regions = regions.regions()
         packed = self._packed_regions(regions)
         if packed is not None:
             arr, n = packed
@@ -431,6 +435,25 @@ class Decoder:
         from .screen import _screen_decoder
         return _screen_decoder(self, kmer_set, min_hits, min_percent, interleaved, keep_matched)
 
+    def overlap(self, *, min_overlap=30, max_mismatches=5, max_mismatch_percent=20, quality_base=33):
+        """Where read 1 and the reverse complement of read 2 of every decoded pair of mates (records 2j and 2j + 1) overlap,
+        found on the GPU (decodes first if nothing is decoded yet) -> Overlaps, which select() takes: every record cut where
+        it reads into the adapter; merge() joins the found pairs.  A shift is accepted with min_overlap matches, at most
+        max_mismatches mismatches and at most max_mismatch_percent of them.  See nafcodec_amd.overlap."""
+        from .overlap import _overlap_decoder
+        return _overlap_decoder(self, min_overlap, max_mismatches, max_mismatch_percent, quality_base)
+
+    def merge(self, overlaps):
+        """The found pairs of `overlaps` (what overlap() of THIS decoder returned) joined into one record each -> a Selection
+        in HBM, in pair order: read 1, then what read 2's reverse complement adds; where both cover a position the letter
+        with the higher quality wins (read 1's on a tie and without qualities) and the qualities are combined as
+        include/nafgpu.h says at nafgpu_overlap.  Id and comment are read 1's.  ValueError for what the rules refuse."""
+        h, res, err = c_void_p(), _ffi.SelectResult(), _ffi.Error()
+        rc = self._lib.c.nafgpu_merge_pairs(self._h, overlaps._handle(), byref(h), byref(res), byref(err))
+        if rc != _ffi.OK:
+            self._raise_select(rc, err)
+        return Selection(self._lib, h, res)
+
 
 class Selection:
     """What Decoder.select() returns: records cut out of a decoded archive, in HBM, with the fields encode_device() reads
@@ -518,6 +541,14 @@ class Selection:
         self._handle()
         return screen(self, kmer_set, min_hits=min_hits, min_percent=min_percent, interleaved=interleaved, keep_matched=keep_matched, device=device,
                       _lib=self._lib)
+
+    def overlap(self, *, min_overlap=30, max_mismatches=5, max_mismatch_percent=20, quality_base=33, device=None):
+        """Where the mates of every selected pair (records 2j and 2j + 1) overlap -> Overlaps (nafcodec_amd.overlap); their
+        records are this selection's."""
+        from .overlap import overlap
+        self._handle()
+        return overlap(self, min_overlap=min_overlap, max_mismatches=max_mismatches, max_mismatch_percent=max_mismatch_percent,
+                       quality_base=quality_base, device=device, _lib=self._lib)
 
     def close(self):
         if self._h is not None:

@@ -250,6 +250,14 @@ class ParsedText:
         return screen(self, kmer_set, min_hits=min_hits, min_percent=min_percent, interleaved=interleaved, keep_matched=keep_matched, device=device,
                       _lib=self._lib)
 
+    def overlap(self, *, min_overlap=30, max_mismatches=5, max_mismatch_percent=20, quality_base=33, device=None):
+        """Where the mates of every parsed pair (records 2j and 2j + 1) overlap -> Overlaps (nafcodec_amd.overlap); their
+        records are the parsed ones."""
+        from .overlap import overlap
+        self._handle()
+        return overlap(self, min_overlap=min_overlap, max_mismatches=max_mismatches, max_mismatch_percent=max_mismatch_percent,
+                       quality_base=quality_base, device=device, _lib=self._lib)
+
     def close(self):
         if self._h is not None:
             h, self._h = self._h, None
